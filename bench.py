@@ -41,6 +41,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # dense bf16, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
+DUMP_MASK_PIXELS = 1 << 15      # --dump-outputs: seeded (y, x) positions per image at which every kept mask is written
 
 
 def parse():
@@ -100,6 +102,10 @@ def parse():
                          "depth=12 -- the marginal cost of a stage inside the pipelined step = the step time with and without it")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="no software pipeline over steps (ViT of step i+1 || tails of step i inside one graph)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what its LAST step delivered to the caller (rank 0: detections of each of its "
+                         "images, a seeded pixel sample of their masks, the gathered records) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; the inputs are seeded, so two builds can be compared array by array")
     return ap.parse_args()
 
 
@@ -300,6 +306,56 @@ def cpu_baseline(model, size, images, text, n_images=3, max_threads=64):
 def _detections_of(out):
     keep = out["det_scores"] >= 0
     return out["det_boxes"][keep].float().cpu(), out["det_scores"][keep].float().cpu(), out["det_classes"][keep].cpu()
+
+
+def dump_outputs(out_dir, last, steps):
+    """--dump-outputs: what the caller of the timed path received from its LAST step, as float32 / float64 .npy files -- per image b of
+    this rank: img{b}_boxes / _scores / _classes / _query_index (every kept detection), img{b}_mask_area (pixels per mask, exact) and
+    img{b}_mask_sample (every mask at P seeded (y, x) positions of the frame, listed in img{b}_mask_sample_yx), the run-length strings
+    when masks leave as COCO RLE, the label map at the same positions plus its exact label histogram (semantic branch), and `records`
+    (the [ranks, B, k, 6] detection records of the exchange).  P is chosen so that everything stays under DUMP_LIMIT_BYTES."""
+    import numpy as np
+
+    if not steps or "out" not in last:
+        raise SystemExit("--dump-outputs needs at least one timed step")
+    os.makedirs(out_dir, exist_ok=True)
+    ticket, (insts, rec) = last["ticket"], last["out"]
+    rec = last.get("records", rec)
+    insts = insts if isinstance(insts, (list, tuple)) else [insts]
+    k = max([len(i) for i in insts] + [1])
+    P = max(256, min(DUMP_MASK_PIXELS, (DUMP_LIMIT_BYTES // 2) // (len(insts) * (k + 1) * 4)))
+    arrays = {}
+    for b, inst in enumerate(insts):
+        fh, fw = inst.image_size
+        arrays[f"img{b}_boxes"] = inst.pred_boxes.tensor.float().numpy()
+        arrays[f"img{b}_scores"] = inst.scores.float().numpy()
+        arrays[f"img{b}_classes"] = inst.pred_classes.double().numpy()
+        if inst.has("query_index"):
+            arrays[f"img{b}_query_index"] = inst.query_index.double().numpy()
+        rng = np.random.default_rng(1000 + b)                 # the same positions in every run with the same frame size
+        ys, xs = torch.from_numpy(rng.integers(0, fh, P)), torch.from_numpy(rng.integers(0, fw, P))
+        if inst.has("pred_masks"):
+            m = inst.pred_masks
+            arrays[f"img{b}_mask_area"] = m.flatten(1).sum(1).double().numpy()
+            arrays[f"img{b}_mask_sample"] = m[:, ys, xs].float().numpy()
+            arrays[f"img{b}_mask_sample_yx"] = torch.stack([ys, xs], 1).double().numpy()
+        if inst.has("pred_masks_rle"):
+            strings = [r["counts"] for r in inst.pred_masks_rle]
+            arrays[f"img{b}_mask_rle_lengths"] = np.array([len(s) for s in strings], dtype=np.float64)
+            arrays[f"img{b}_mask_rle_bytes"] = np.frombuffer(b"".join(strings), dtype=np.uint8).astype(np.float32)
+        labels = getattr(ticket, "sem_labels", None)
+        if labels is not None:
+            lab = labels[b].long()
+            arrays[f"img{b}_sem_label_hist"] = torch.bincount(lab.flatten(), minlength=256).double().numpy()
+            arrays[f"img{b}_sem_label_sample"] = lab[ys, xs].float().numpy()
+    if rec is not None:
+        arrays["records"] = rec.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": total, "images": len(insts), "mask_sample_pixels": P}
 
 
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
@@ -638,12 +694,20 @@ def main():
     # copy stream meanwhile); 2 with the software pipeline, where a ticket's detections are produced by the next step's replay
     depth = 1 if args.no_pipeline else 2
 
-    def timed_region(runner, warmup, steps, collective=True, trace=None):
+    def timed_region(runner, warmup, steps, collective=True, trace=None, last=None):
         """`warmup` untimed steps, then EXACTLY `steps` steps (the last one flushed inside the region) between barrier +
         synchronize on both sides; returns this rank's seconds.  runner: the DataParallelRunner (records / runs exchanged), or the
-        GraphedForward itself (the same step with no exchange: the same-process N = 1 reference of an N-rank run)."""
+        GraphedForward itself (the same step with no exchange: the same-process N = 1 reference of an N-rank run).
+        `last` (a dict): receives the ticket and the result of the last collected step (references only, no copy)."""
         queue = []
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(warmup + steps + 2)] if trace is not None else None
+
+        def collect():
+            ticket = queue.pop(0)
+            out = runner.result(ticket)
+            if last is not None:
+                last["ticket"], last["out"] = ticket, out
+            return out
 
         def step(i):
             if raw_images is not None:
@@ -654,13 +718,15 @@ def main():
             else:
                 batch = [images[(i * B + b) % len(images)] for b in range(B)]
                 queue.append(runner.submit(batch if B > 1 else batch[0], text))
-            return runner.result(queue.pop(0)) if len(queue) > depth else None
+            return collect() if len(queue) > depth else None
 
         def flush():
             while queue:
-                runner.result(queue.pop(0))
+                collect()
             if hasattr(runner, "drain"):
-                runner.drain()
+                rec = runner.drain()
+                if last is not None and rec is not None:        # lagged exchange: the last step's gathered records arrive here
+                    last["records"] = rec
 
         # `trace` (a dict): stream-side milliseconds of every step, warm-up included -- an event recorded on the compute stream behind each
         # submit (no host wait: the region is timed exactly as without it); what the driver's short command pays per step, in order
@@ -696,7 +762,12 @@ def main():
     if args.instrumented_only:
         args.warmup = args.steps = 0
     step_trace = {} if (args.steps and args.steps + args.warmup <= 400) else None
-    elapsed_rank = elapsed = timed_region(dp, args.warmup, args.steps, trace=step_trace)
+    last = {} if args.dump_outputs else None
+    elapsed_rank = elapsed = timed_region(dp, args.warmup, args.steps, trace=step_trace, last=last)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # right behind the region, before any other step reuses the slot buffers the last step's masks are views of
+        dumped = dump_outputs(args.dump_outputs, last, args.steps)
     per_rank = None
     if dist is not None:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -839,6 +910,8 @@ def main():
             result.update(f16)
         if step_trace:
             result["step_trace"] = step_trace
+        if dumped is not None:
+            result["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             try:
                 timed = [im.contiguous() for im in images[:max(1, args.cpu_images)]]

@@ -118,3 +118,43 @@ def test_kernel_family_folds_the_tile_kernels_instantiations():
     assert fam("gemm_bf16_kres_kernel<0, false, true>") == "gemm_bf16_kres_kernel<0, false, true>"
     # round 6: the in-launch-statistics flavour of the 256 x 128 tile kernel belongs to ITS family, not to the 256 x 256 one and not to none
     assert fam("gemm_bf16_p8_kernel<128, true, rowstat>") == "gemm_bf16_p8_kernel<128, true>" != fam("gemm_bf16_p8_kernel<256, true, persistent>")
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_as_float_npy(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the last collected step's detections, a seeded pixel sample of every kept mask with the
+    masks' exact areas, run-length strings and the records, as float32 / float64 .npy files under the size limit; the sample positions
+    are the same in every run"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from ape_amd.structures import make_instances
+
+    def step(seed):
+        g = torch.Generator().manual_seed(seed)
+        insts = []
+        for n, (h, w) in ((3, (64, 80)), (0, (48, 48))):
+            masks = torch.rand(n, h, w, generator=g) > 0.5
+            rle = [{"size": [h, w], "counts": bytes([65 + i, 66, 67])} for i in range(n)]
+            insts.append(make_instances((h, w), torch.rand(n, 4, generator=g) * 40, torch.rand(n, generator=g), torch.arange(n),
+                                        masks, query_index=torch.arange(n) * 7, pred_masks_rle=rle))
+        return {"ticket": object(), "out": (insts, torch.rand(2, 3, 6, generator=g))}
+
+    last = step(0)
+    got = bench.dump_outputs(str(tmp_path / "a"), last, steps=5)
+    bench.dump_outputs(str(tmp_path / "b"), step(0), steps=5)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert got["arrays"] == len(names) and got["bytes"] <= bench.DUMP_LIMIT_BYTES and names == sorted(os.listdir(tmp_path / "b"))
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        assert np.array_equal(a, np.load(tmp_path / "b" / n)), n
+    inst = last["out"][0][0]
+    m = inst.pred_masks
+    yx = np.load(tmp_path / "a" / "img0_mask_sample_yx.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "img0_mask_sample.npy"), m[:, yx[:, 0], yx[:, 1]].float().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "img0_mask_area.npy"), m.flatten(1).sum(1).double().numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "img0_boxes.npy"), inst.pred_boxes.tensor.numpy())
+    assert np.load(tmp_path / "a" / "img1_scores.npy").shape == (0,)
+    assert np.load(tmp_path / "a" / "img0_mask_rle_bytes.npy").tolist() == [65, 66, 67, 66, 66, 67, 67, 66, 67]
+    assert np.array_equal(np.load(tmp_path / "a" / "records.npy"), last["out"][1].numpy())

@@ -1,9 +1,11 @@
 """Drop-in contract at the LazyConfig level: every keyword the reference's APE-L_D / APE-Ti configuration chain passes
 to a hot-path class -- `L(Class)(kw=...)` calls and later `model.model_vision[.transformer[.encoder|.decoder]].<kw> = ...`
-assignments -- is accepted by the HIP-backed class of the same name.  Static (AST) check of the reference's config files; needs
-the reference checkout."""
+assignments -- is accepted by the HIP-backed class of the same name.  Static (AST) check of the reference's config files: read
+live from the reference checkout when there is one (and then also checked against the fixture), otherwise from the keyword
+fixture tests/golden/config_kwargs.json (tests/golden/make_config_kwargs.py)."""
 import ast
 import inspect
+import json
 import os
 import re
 
@@ -24,11 +26,18 @@ CHAINS = {
     "G_A": ["common/backbone/vitg_eva01_clip_1024.py", "common/backbone/vitg_eva01_clip_1536.py", "common/backbone/vite_eva02_clip_1024.py"],
     "V_A": ["common/backbone/vitg_eva01.py", "common/backbone/vitg_eva01_1536.py"],
 }
-# config class name -> (our class, attribute path whose later assignments also count)
-pytestmark = pytest.mark.skipif(not os.path.isdir(CFG), reason="needs the reference checkout")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_kwargs.json")
+_FIXTURE = []
 
 
-def _collect(files):
+def _fixture():
+    if not _FIXTURE:
+        with open(FIXTURE) as fh:
+            _FIXTURE.append(json.load(fh))
+    return _FIXTURE[0]
+
+
+def _live_collect(files):
     calls, assigns = {}, {}
     for rel in files:
         path = os.path.join(CFG, rel)
@@ -46,6 +55,35 @@ def _collect(files):
     return calls, assigns
 
 
+def _collect(chain):
+    """(keywords per called config class, attributes assigned per model_vision path) of one configuration chain"""
+    fx = _fixture()["chains"][chain]
+    calls, assigns = ({k: set(v) for k, v in fx["calls"].items()}, {k: set(v) for k, v in fx["assigns"].items()})
+    if os.path.isdir(CFG):
+        assert (calls, assigns) == _live_collect(CHAINS[chain]), f"{FIXTURE} is stale: rerun tests/golden/make_config_kwargs.py"
+    return calls, assigns
+
+
+def _live_overrides():
+    """every `model.model_vision[.transformer[.encoder|.decoder]].<kw> = ...` of configs/**/ape_deta/*vit[lt]_eva02*.py:
+    {"files": [config file], "lines": [[path, kw, index of the file]]}"""
+    import glob
+    files = sorted(glob.glob(os.path.join(CFG, "**", "ape_deta", "*vit[lt]_eva02*.py"), recursive=True))
+    lines = []
+    for i, f in enumerate(files):
+        for m in re.finditer(r"^model\.model_vision((?:\.\w+)*)\.(\w+)\s*=", open(f).read(), flags=re.M):
+            if m.group(1) in ("", ".transformer", ".transformer.encoder", ".transformer.decoder"):
+                lines.append([m.group(1), m.group(2), i])
+    return {"files": [os.path.relpath(f, CFG) for f in files], "lines": lines}
+
+
+def _overrides():
+    fx = _fixture()["overrides"]
+    if os.path.isdir(CFG):
+        assert fx == _live_overrides(), f"{FIXTURE} is stale: rerun tests/golden/make_config_kwargs.py"
+    return fx
+
+
 def _accepts(cls):
     sig = inspect.signature(cls.__init__)
     if any(p.kind == p.VAR_KEYWORD for p in sig.parameters.values()):
@@ -61,7 +99,7 @@ def test_every_config_keyword_is_accepted(chain):
     from ape_amd.modeling.backbone import vit_eva, vit_eva02, vit_eva_clip
     from ape_amd.modeling.text import EVA02CLIP
 
-    calls, assigns = _collect(CHAINS[chain])
+    calls, assigns = _collect(chain)
     vit_mod = vit_eva_clip if chain in ("L_D", "G_A") else vit_eva if chain == "V_A" else vit_eva02
     table = [
         (("DeformableDETRSegm", "DeformableDETRSegmVL"), "", DeformableDETRSegmVL),
@@ -96,19 +134,17 @@ def test_every_config_keyword_is_accepted(chain):
 def test_overrides_of_every_vit_ape_config_are_accepted():
     """all configs/**/ape_deta/*vit[lt]_eva02*.py (APE-Ti, APE-L_A..D, every dataset mix): each `model.model_vision[.transformer
     [.encoder|.decoder]].<kw> = ...` override names a constructor keyword of the HIP-backed class"""
-    import glob
     from ape_amd.modeling.ape_deta import (DeformableDETRSegmVL, DeformableDetrTransformerDecoderVL, DeformableDetrTransformerEncoderVL,
                                            DeformableDetrTransformerVL)
     acc = {"": DeformableDETRSegmVL, ".transformer": DeformableDetrTransformerVL, ".transformer.encoder": DeformableDetrTransformerEncoderVL,
            ".transformer.decoder": DeformableDetrTransformerDecoderVL}
     ok = {k: set(inspect.signature(c.__init__).parameters) for k, c in acc.items()}
-    files = glob.glob(os.path.join(CFG, "**", "ape_deta", "*vit[lt]_eva02*.py"), recursive=True)
-    assert len(files) > 50
+    ov = _overrides()
+    assert len(ov["files"]) > 50
     bad, n = {}, 0
-    for f in files:
-        for m in re.finditer(r"^model\.model_vision((?:\.\w+)*)\.(\w+)\s*=", open(f).read(), flags=re.M):
-            if m.group(1) in ok:
-                n += 1
-                if m.group(2) not in ok[m.group(1)]:
-                    bad.setdefault((m.group(1), m.group(2)), []).append(os.path.basename(f))
+    for path, kw, i in ov["lines"]:
+        if path in ok:
+            n += 1
+            if kw not in ok[path]:
+                bad.setdefault((path, kw), []).append(os.path.basename(ov["files"][i]))
     assert not bad and n > 500, (bad, n)
