@@ -22,11 +22,14 @@ broadcast once from rank 0 (RCCL) and each step's fixed-size detection records -
 lengths (--mask-format rle, the default for N > 1) -- are all-gathered (RCCL over xGMI), asynchronously: the host awaits step
 i's exchange while step i + 1 computes.  scaling = weak (B images per rank per step).
 
-Extra objects on the JSON line: `roofline` for the dominant kernel (the bf16 MFMA GEMM, measured with HIP events on
-the launch stream in an instrumented pass right after the timed region), `cpu_baseline` (the oracle -- a CPU port
-of the reference algorithm -- one full-depth image timed on the host cores of the same box, rank 0, N = 1 only) and
-`parity` (the bf16 pipeline's heads / detections on image 0 against that oracle forward, and COCO box AP of the bf16
-detections against the fp32 pipeline's detections as pseudo ground truth over `--ap-images` seeded images).
+A plain run does what the headline needs and no more: set up, warm up, time the K steps, write `--dump-outputs`, print the
+line (`value`, `ms_per_step`, the per-step `step_trace` and per-rank rates the timed region records; `efficiency_vs_n1` when
+`--n1-value` is given).  `--full` adds what takes runs of its own, after the timed region (`extra_legs`): `value_f16` (the same
+step in IEEE half, its own timed region, N = 1), `roofline` for the dominant kernel (the bf16 MFMA GEMM, measured with HIP events
+on the launch stream in an instrumented pass), `cpu_baseline` (the oracle -- a CPU port of the reference algorithm -- full-depth
+images timed on the host cores of the same box, rank 0, N = 1 only), `parity` (the bf16 pipeline's heads / detections on those
+images against the oracle forwards, and COCO box AP of the bf16 detections against the fp32 pipeline's detections as pseudo
+ground truth over `--ap-images` seeded images) and, for N > 1 without `--n1-value`, the same-process N = 1 reference.
 """
 import argparse
 import json
@@ -50,9 +53,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)       # 100 two-image steps = a timed region of ~2.2 s
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run what takes runs of its own: the f16 region (value_f16), the instrumented "
+                         "pass (roofline), the CPU oracle (cpu_baseline, parity) and, N > 1 without --n1-value, the N = 1 reference")
     ap.add_argument("--size", default="L_D_coco", help="L_D_coco = APE-L_D with the COCO config's top-100 (BASELINE config 2); L_D = top-300")
     ap.add_argument("--classes", type=int, default=80)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle (cpu_baseline, parity)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--stream-images", type=int, default=8, help="distinct synthetic images cycled per rank")
     ap.add_argument("--images-per-step", type=int, default=2,
@@ -68,9 +74,9 @@ def parse():
     ap.add_argument("--dry", action="store_true",
                     help="launch + exchange check without a GPU: the ranks start, rendezvous (use --backend gloo), broadcast a text "
                          "bank and all-gather K steps of synthetic detection records on the CPU; no forward runs and `value` is null")
-    ap.add_argument("--cpu-images", type=int, default=3, help="images the CPU oracle times after its warm-up pass (cpu_baseline)")
+    ap.add_argument("--cpu-images", type=int, default=3, help="--full: images the CPU oracle times after its warm-up pass (cpu_baseline)")
     ap.add_argument("--ap-images", type=int, default=16,
-                    help="seeded images for the box-AP parity number (bf16 detections vs the fp32 pipeline's as pseudo ground truth)")
+                    help="--full: seeded images for the box-AP parity number (bf16 detections vs the fp32 pipeline's as pseudo ground truth)")
     ap.add_argument("--input", choices=["resident", "uint8"], default="resident",
                     help="resident: float32 model-ready images already in HBM (the tier's definition of `value`); uint8: the predictor's "
                          "input side inside the timed region (ape/engine/defaults.py:213-222) -- ORIGINAL uint8 BGR images (1.25 x the model "
@@ -83,17 +89,18 @@ def parse():
                          "host) plus the exchange (north_star: all-gather of boxes / masks), so the driver's 1 -> N efficiency compares like with like")
     ap.add_argument("--n1-value", type=float, default=None,
                     help="N > 1: the images/sec of the N = 1 run of the same workload (e.g. the driver's previous line): efficiency_vs_n1 = "
-                         "value / (N x this).  Without it rank 0 measures the reference itself, in the same process, right after the timed "
-                         "region (--solo-steps steps of the same step with no exchange while the other ranks wait at a barrier)")
-    ap.add_argument("--solo-steps", type=int, default=20, help="N > 1 without --n1-value: steps of the same-process N = 1 reference on rank 0")
+                         "value / (N x this).  Without it, --full makes rank 0 measure the reference itself, in the same process, right after "
+                         "the timed region (--solo-steps steps of the same step with no exchange while the other ranks wait at a barrier)")
+    ap.add_argument("--solo-steps", type=int, default=20, help="--full, N > 1 without --n1-value: steps of the same-process N = 1 reference on rank 0")
     ap.add_argument("--no-second-flavour", action="store_true",
-                    help="skip the second timed region of the default bf16 run: the SAME step in IEEE half (--dtype f16's pipeline, the "
+                    help="skip the second timed region of a --full bf16 run: the SAME step in IEEE half (--dtype f16's pipeline, the "
                          "reference's own evaluation dtype), --f16-steps steps, reported as value_f16 / ms_per_step_f16 (N = 1 only)")
     ap.add_argument("--f16-steps", type=int, default=0, help="0 = the same number of steps (and the same warm-up) as the bf16 region")
     ap.add_argument("--dry-images", type=int, default=1000, help="--dry: length of the sharded synthetic stream")
     ap.add_argument("--instrumented-only", action="store_true",
                     help="skip the timed region: run only the instrumented pass that produces `roofline` (what tools/gpu_profile.sh puts "
-                         "under rocprofv3 --kernel-trace --stats, so that the trace holds exactly the launches the HIP events metered)")
+                         "under rocprofv3 --kernel-trace --stats, so that the trace holds exactly the launches the HIP events metered); "
+                         "implies --full")
     ap.add_argument("--dtype", choices=["bf16", "f16"], default="bf16",
                     help="16-bit flavour of the timed pipeline: bf16 = BASELINE's dtype (default); f16 = IEEE half operands, the reference's "
                          "own evaluation dtype (tools/train_net.py:642) -- same kernels, v_mfma_f32_16x16x32_f16, 3 more mantissa bits")
@@ -107,6 +114,17 @@ def parse():
                          "images, a seeded pixel sample of their masks, the gathered records) as DIR/<name>.npy, float32 / float64, "
                          f"at most {DUMP_LIMIT_BYTES >> 20} MB in all; the inputs are seeded, so two builds can be compared array by array")
     return ap.parse_args()
+
+
+def extra_legs(args, world):
+    """which of the runs that follow the timed region this invocation makes: none without --full (--instrumented-only implies it)
+    -- a plain run's line is the headline and what the timed region itself records"""
+    full = args.full or args.instrumented_only
+    timed = args.steps > 0 and not args.instrumented_only
+    return {"second_flavour": full and timed and world == 1 and args.dtype == "bf16" and not args.no_second_flavour,
+            "roofline": full,
+            "cpu_baseline": full and world == 1 and not args.no_cpu_baseline,
+            "n1_solo": full and timed and world > 1 and not args.n1_value}
 
 
 def make_images(n, S, seed, device):
@@ -260,6 +278,76 @@ def pmc_traffic_bytes(kernel):
     return None, "no PMC summary under profiles/"
 
 
+def roofline_object(mv, images, text, B, sem_meta):
+    """`roofline` (--full): an instrumented pass (eager, NOT part of the timed region) of the SAME step composition as the timed
+    steps -- one batched ViT pass over B images, then B tails -- with every branch inline, so each GEMM runs alone between its HIP
+    events; grouped by the kernel symbol the library reports.  The object is about the symbol with the largest total."""
+    import ape_amd.ops as ops
+
+    reps = 3
+    n_tok = (mv.backbone.net.img_size // mv.backbone.net.patch_size) ** 2
+
+    def eager_step(i):
+        batch = [images[(i * B + b) % len(images)].contiguous() for b in range(B)]
+        x = mv.backbone.net.forward_tokens(batch if B > 1 else batch[0], mv._mean, mv._std)
+        for b in range(B):
+            out = mv.forward_single(batch[b], text, vit_feat=x[b * n_tok:(b + 1) * n_tok], semantic=sem_meta)
+            hh, ww = batch[b].shape[-2:]
+            mv.postprocess_instance(out, (hh, ww), hh, ww)
+
+    with ops.inline_forks():
+        # one unmetered pass first: the timed region replayed a graph (private memory pool), so the first EAGER pass makes the
+        # caching allocator hipMalloc its blocks -- a host stall of tens of ms that would land between an event pair while
+        # the GPU sits idle (seen once: one K = 256 GEMM "took" 44 ms and became the dominant symbol)
+        eager_step(0)
+        torch.cuda.synchronize()
+        with GemmMeter(ops) as meter:
+            for i in range(reps):
+                eager_step(i)
+            groups = meter.summary()
+    reps = reps * B                                     # images in the instrumented pass
+    dom_name, (dom_n, dom_t, dom_fl, dom_pair) = groups[0]
+    all_t, all_fl = sum(g[1][1] for g in groups), sum(g[1][2] for g in groups)
+    achieved = dom_fl / dom_t / 1e12
+    traffic, traffic_note = pmc_traffic_bytes(dom_name)
+    return {"bound": "mfma", "kernel": dom_name, "achieved": achieved,
+            "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
+            "traffic": traffic, "traffic_source": traffic_note, "launches_per_image": dom_n / reps,
+            "avg_launch_us": 1e6 * dom_t / max(dom_n, 1), "kernel_ms_per_image": 1e3 * dom_t / reps,
+            "flops_per_launch": dom_fl / max(dom_n, 1),
+            # every family of the eight-wave tile kernel (template gemm_bf16_p8_kernel, folded by tile width): the figures of the
+            # family the object is NOT about stay on the line
+            "tile_kernel_families": {k: {"kernel_ms_per_image": round(1e3 * v[1] / reps, 3), "launches_per_image": round(v[0] / reps, 2),
+                                         "avg_launch_us": round(1e6 * v[1] / max(v[0], 1), 2), "tflops": round(v[2] / v[1] / 1e12, 1),
+                                         "frac": round(v[2] / v[1] / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)}
+                                     for k, v in groups if "_p8_kernel<" in k},
+            "avg_launch_us_event_pair": 1e6 * dom_pair / max(dom_n, 1), "frac_event_pair": dom_fl / dom_pair / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+            "metering": "an eager pass of the step's composition, every branch inline (one kernel at a time, stand-alone launch "
+                        "durations); each launch carries its OWN (start, stop) HIP events (hipExtLaunchKernelGGL through the library's "
+                        "launch meter, csrc/meter.cpp): their elapsed time is the dispatch's begin-to-end duration, the number "
+                        "rocprofv3's kernel trace reports for the same launch (profiles/).  `avg_launch_us_event_pair` / "
+                        "`frac_event_pair` = the round-1..4 method, an event pair RECORDED around the call: it adds the "
+                        "command-processor gaps either side of the kernel",
+            # the dominant family per problem shape M x N x K (launches per image, average us, TFLOP/s)
+            "by_shape": {sh: {"launches_per_image": round(v[0] / reps, 2), "avg_launch_us": round(1e6 * v[1] / max(v[0], 1), 1),
+                              "tflops": round(v[2] / v[1] / 1e12, 1)}
+                         for (fam, sh), v in sorted(meter.shapes.items(), key=lambda kv: -kv[1][1]) if fam == dom_name},
+            "all_gemm_kernels": {"ms_per_image": 1e3 * all_t / reps, "tflops": all_fl / all_t / 1e12,
+                                 "flops_per_image": all_fl / reps,
+                                 "by_kernel_ms_per_image": {k: round(1e3 * v[1] / reps, 3) for k, v in groups},
+                                 "by_kernel_tflops": {k: round(v[2] / v[1] / 1e12, 1) for k, v in groups},
+                                 "by_kernel_launches_per_image": {k: round(v[0] / reps, 2) for k, v in groups},
+                                 # every (kernel family, M x N x K) with >= 0.05 ms per image: launches, average us, TFLOP/s
+                                 # every kernel the library launched in the instrumented pass, by launch-site expression
+                                 # (non-GEMM kernels included): [launches per image, average us, ms per image], >= 0.05 ms
+                                 "library_kernels": {k: [round(v[0] / reps, 2), round(1e6 * v[1] / max(v[0], 1), 1), round(1e3 * v[1] / reps, 3)]
+                                                     for k, v in sorted(meter.kernels.items(), key=lambda kv: -kv[1][1])
+                                                     if 1e3 * v[1] / reps >= 0.05},
+                                 "by_kernel_and_shape": {f"{fam} {sh}": [round(v[0] / reps, 2), round(1e6 * v[1] / max(v[0], 1), 1), round(v[2] / v[1] / 1e12, 1)]
+                                                         for (fam, sh), v in sorted(meter.shapes.items(), key=lambda kv: -kv[1][1])
+                                                         if 1e3 * v[1] / reps >= 0.05}}}
+
+
 def cpu_baseline(model, size, images, text, n_images=3, max_threads=64):
     """The oracle (CPU port of the reference algorithm, oracle/ape_oracle.py) on the host cores of this box: one warm-up pass
     through a depth-reduced copy (thread pool / primitive caches), then `n_images` full-depth fp32 forwards, each timed.  The
@@ -271,7 +359,9 @@ def cpu_baseline(model, size, images, text, n_images=3, max_threads=64):
     cfg = dict(CONFIGS[size])
     depth, enc, dec = cfg["depth"], cfg["enc_layers"], cfg["dec_layers"]
     sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items()}
-    cores = min(os.cpu_count() or 1, max_threads)
+    # the intra-op pool as the environment sizes it (OMP_NUM_THREADS, else torch's default), not one thread per CPU the box reports:
+    # where a job may use only some of a large host's CPUs, a pool of os.cpu_count() threads oversubscribes them
+    cores = min(torch.get_num_threads(), max_threads)
     torch.set_num_threads(cores)
     txt = text.cpu()
     warm = dict(cfg, depth=3, enc_layers=1, dec_layers=1)
@@ -638,7 +728,6 @@ def main():
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         dist.init_process_group(args.backend, device_id=dev if args.backend == "nccl" else None)
 
-    import ape_amd.ops as ops
     from ape_amd.modeling.build import build_ape, init_synthetic
     from ape_amd.runtime import GraphedForward
 
@@ -761,6 +850,7 @@ def main():
 
     if args.instrumented_only:
         args.warmup = args.steps = 0
+    legs = extra_legs(args, world)
     step_trace = {} if (args.steps and args.steps + args.warmup <= 400) else None
     last = {} if args.dump_outputs else None
     elapsed_rank = elapsed = timed_region(dp, args.warmup, args.steps, trace=step_trace, last=last)
@@ -780,21 +870,20 @@ def main():
             per_rank = [round(float(v.item()), 2) for v in every]     # each rank's own images/sec between the two barriers
 
     # N > 1: the N = 1 reference of the efficiency -- given (--n1-value, e.g. the driver's N = 1 line) or measured here: rank 0 alone
-    # runs the SAME step with no exchange (every other GPU idle at a barrier), right after the timed region, same process, warm
+    # runs the SAME step with no exchange (every other GPU idle at a barrier), right after the timed region, same process, warm (--full)
     n1 = None
-    if world > 1 and args.steps:
-        if args.n1_value:
-            n1 = {"value": float(args.n1_value), "source": "--n1-value"}
-        else:
-            if rank == 0:
-                sec = timed_region(graphed, 2, args.solo_steps, collective=False)
-                n1 = {"value": args.solo_steps * B / sec, "source": f"same process: rank 0 alone, {args.solo_steps} steps of the same step with no "
-                                                                    "exchange, the other ranks idle at a barrier"}
-            dist.barrier()
+    if world > 1 and args.steps and args.n1_value:
+        n1 = {"value": float(args.n1_value), "source": "--n1-value"}
+    elif legs["n1_solo"]:
+        if rank == 0:
+            sec = timed_region(graphed, 2, args.solo_steps, collective=False)
+            n1 = {"value": args.solo_steps * B / sec, "source": f"same process: rank 0 alone, {args.solo_steps} steps of the same step with no "
+                                                                "exchange, the other ranks idle at a barrier"}
+        dist.barrier()
 
-    # second flavour of the default run: the same step in IEEE half (the reference's own evaluation dtype), timed in the same invocation
+    # second flavour of a --full bf16 run: the same step in IEEE half (the reference's own evaluation dtype), timed in the same invocation
     f16 = None
-    if world == 1 and args.dtype == "bf16" and args.steps and not args.no_second_flavour and not args.instrumented_only:
+    if legs["second_flavour"]:
         mv.set_compute_dtype(torch.float16)
         g16 = GraphedForward(mv, use_graph=not args.no_graph, images_per_step=B, batch_vit=not args.no_batch_vit,
                              pipeline=not args.no_pipeline, any_size=args.stream == "coco", semantic=sem_meta, mask_format=mask_format,
@@ -812,35 +901,7 @@ def main():
 
     result = None
     if rank == 0:
-        # instrumented pass (eager, NOT part of the timed region): the SAME step composition as the timed steps -- one batched
-        # ViT pass over B images, then B tails -- with every branch inline, so each GEMM runs alone between its HIP events;
-        # grouped by the kernel symbol the library reports.  The roofline object is about the symbol with the largest total.
-        reps = 3
-        n_tok = (mv.backbone.net.img_size // mv.backbone.net.patch_size) ** 2
-
-        def eager_step(i):
-            batch = [images[(i * B + b) % len(images)].contiguous() for b in range(B)]
-            x = mv.backbone.net.forward_tokens(batch if B > 1 else batch[0], mv._mean, mv._std)
-            for b in range(B):
-                out = mv.forward_single(batch[b], text, vit_feat=x[b * n_tok:(b + 1) * n_tok], semantic=sem_meta)
-                hh, ww = batch[b].shape[-2:]
-                mv.postprocess_instance(out, (hh, ww), hh, ww)
-
-        with ops.inline_forks():
-            # one unmetered pass first: the timed region replayed a graph (private memory pool), so the first EAGER pass makes the
-            # caching allocator hipMalloc its blocks -- a host stall of tens of ms that would land between an event pair while
-            # the GPU sits idle (seen once: one K = 256 GEMM "took" 44 ms and became the dominant symbol)
-            eager_step(0)
-            torch.cuda.synchronize()
-            with GemmMeter(ops) as meter:
-                for i in range(reps):
-                    eager_step(i)
-                groups = meter.summary()
-        reps = reps * B                                     # images in the instrumented pass
-        dom_name, (dom_n, dom_t, dom_fl, dom_pair) = groups[0]
-        all_t, all_fl = sum(g[1][1] for g in groups), sum(g[1][2] for g in groups)
-        achieved = dom_fl / dom_t / 1e12
-        traffic, traffic_note = pmc_traffic_bytes(dom_name)
+        roofline = roofline_object(mv, images, text, B, sem_meta) if legs["roofline"] else None
         result = {
             "metric": f"images/sec @{S}^2 APE-L_D fwd", "value": (world * args.steps * B / elapsed) if args.steps else None, "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": (1e3 * elapsed / args.steps) if args.steps else None,
@@ -863,43 +924,9 @@ def main():
                            + mv.test_topk_per_image * 32) / 1e6, 1),
                        "batched_vit": not args.no_batch_vit, "stream": args.stream,
                        "software_pipeline": (not args.no_pipeline) and "ViT of step i+1 overlaps the tails of step i; the last step is flushed inside the timed region"},
-            "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": achieved,
-                         "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_source": traffic_note, "launches_per_image": dom_n / reps,
-                         "avg_launch_us": 1e6 * dom_t / max(dom_n, 1), "kernel_ms_per_image": 1e3 * dom_t / reps,
-                         "flops_per_launch": dom_fl / max(dom_n, 1),
-                         # every family of the eight-wave tile kernel (template gemm_bf16_p8_kernel, folded by tile width): the figures of the
-                         # family the object is NOT about stay on the line
-                         "tile_kernel_families": {k: {"kernel_ms_per_image": round(1e3 * v[1] / reps, 3), "launches_per_image": round(v[0] / reps, 2),
-                                                      "avg_launch_us": round(1e6 * v[1] / max(v[0], 1), 2), "tflops": round(v[2] / v[1] / 1e12, 1),
-                                                      "frac": round(v[2] / v[1] / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4)}
-                                                  for k, v in groups if "_p8_kernel<" in k},
-                         "avg_launch_us_event_pair": 1e6 * dom_pair / max(dom_n, 1), "frac_event_pair": dom_fl / dom_pair / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-                         "metering": "an eager pass of the step's composition, every branch inline (one kernel at a time, stand-alone launch "
-                                     "durations); each launch carries its OWN (start, stop) HIP events (hipExtLaunchKernelGGL through the library's "
-                                     "launch meter, csrc/meter.cpp): their elapsed time is the dispatch's begin-to-end duration, the number "
-                                     "rocprofv3's kernel trace reports for the same launch (profiles/).  `avg_launch_us_event_pair` / "
-                                     "`frac_event_pair` = the round-1..4 method, an event pair RECORDED around the call: it adds the "
-                                     "command-processor gaps either side of the kernel",
-                         # the dominant family per problem shape M x N x K (launches per image, average us, TFLOP/s)
-                         "by_shape": {sh: {"launches_per_image": round(v[0] / reps, 2), "avg_launch_us": round(1e6 * v[1] / max(v[0], 1), 1),
-                                           "tflops": round(v[2] / v[1] / 1e12, 1)}
-                                      for (fam, sh), v in sorted(meter.shapes.items(), key=lambda kv: -kv[1][1]) if fam == dom_name},
-                         "all_gemm_kernels": {"ms_per_image": 1e3 * all_t / reps, "tflops": all_fl / all_t / 1e12,
-                                              "flops_per_image": all_fl / reps,
-                                              "by_kernel_ms_per_image": {k: round(1e3 * v[1] / reps, 3) for k, v in groups},
-                                              "by_kernel_tflops": {k: round(v[2] / v[1] / 1e12, 1) for k, v in groups},
-                                              "by_kernel_launches_per_image": {k: round(v[0] / reps, 2) for k, v in groups},
-                                              # every (kernel family, M x N x K) with >= 0.05 ms per image: launches, average us, TFLOP/s
-                                              # every kernel the library launched in the instrumented pass, by launch-site expression
-                                              # (non-GEMM kernels included): [launches per image, average us, ms per image], >= 0.05 ms
-                                              "library_kernels": {k: [round(v[0] / reps, 2), round(1e6 * v[1] / max(v[0], 1), 1), round(1e3 * v[1] / reps, 3)]
-                                                                  for k, v in sorted(meter.kernels.items(), key=lambda kv: -kv[1][1])
-                                                                  if 1e3 * v[1] / reps >= 0.05},
-                                              "by_kernel_and_shape": {f"{fam} {sh}": [round(v[0] / reps, 2), round(1e6 * v[1] / max(v[0], 1), 1), round(v[2] / v[1] / 1e12, 1)]
-                                                                      for (fam, sh), v in sorted(meter.shapes.items(), key=lambda kv: -kv[1][1])
-                                                                      if 1e3 * v[1] / reps >= 0.05}}},
         }
+        if roofline is not None:
+            result["roofline"] = roofline
         if args.steps:
             result["per_rank_images_per_s"] = per_rank if per_rank is not None else [round(result["value"], 2)]
         if n1 is not None:
@@ -912,7 +939,7 @@ def main():
             result["step_trace"] = step_trace
         if dumped is not None:
             result["dump_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             try:
                 timed = [im.contiguous() for im in images[:max(1, args.cpu_images)]]
                 result["cpu_baseline"], O = cpu_baseline(model, args.size, timed, text, n_images=args.cpu_images)
@@ -924,7 +951,7 @@ def main():
                 mv.set_compute_dtype(DTYPES[args.dtype])
             except Exception as exc:  # the baseline must never take the GPU number down with it
                 import traceback
-                result.setdefault("cpu_baseline", {"value": None, "unit": "images/sec", "cores": os.cpu_count(), "kind": "port",
+                result.setdefault("cpu_baseline", {"value": None, "unit": "images/sec", "cores": torch.get_num_threads(), "kind": "port",
                                                    "sample": f"failed: {type(exc).__name__}: {exc}"})
                 result.setdefault("parity", {"failed": f"{type(exc).__name__}: {exc}", "trace": traceback.format_exc()[-600:]})
         print(json.dumps(result), flush=True)

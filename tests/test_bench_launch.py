@@ -158,3 +158,27 @@ def test_dump_outputs_writes_the_last_steps_arrays_as_float_npy(tmp_path):
     assert np.load(tmp_path / "a" / "img1_scores.npy").shape == (0,)
     assert np.load(tmp_path / "a" / "img0_mask_rle_bytes.npy").tolist() == [65, 66, 67, 66, 66, 67, 67, 66, 67]
     assert np.array_equal(np.load(tmp_path / "a" / "records.npy"), last["out"][1].numpy())
+
+
+def test_a_plain_run_runs_nothing_after_the_timed_region_and_full_keeps_every_leg(monkeypatch):
+    """`bench.py --gpus N --steps K --warmup W` sets up, warms up, times the K steps and prints the line; the f16 region (value_f16),
+    the instrumented pass (roofline), the CPU oracle (cpu_baseline, parity) and the same-process N = 1 reference of an N-rank run
+    follow the timed region only with --full (bench.extra_legs), and there exactly as before; --instrumented-only implies --full"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def legs(*argv, world=1):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.extra_legs(bench.parse(), world)
+
+    none = {"second_flavour": False, "roofline": False, "cpu_baseline": False, "n1_solo": False}
+    assert legs("--gpus", "1", "--steps", "20", "--warmup", "5") == none
+    assert legs("--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", "out") == none
+    assert legs("--gpus", "8", "--steps", "20", "--warmup", "5", world=8) == none
+    assert legs("--gpus", "1", "--steps", "20", "--warmup", "5", "--full") == dict(none, second_flavour=True, roofline=True, cpu_baseline=True)
+    assert legs("--gpus", "8", "--full", world=8) == dict(none, roofline=True, n1_solo=True)
+    assert legs("--gpus", "8", "--full", "--n1-value", "115", world=8) == dict(none, roofline=True)
+    assert legs("--full", "--dtype", "f16") == dict(none, roofline=True, cpu_baseline=True)
+    assert legs("--full", "--no-cpu-baseline", "--no-second-flavour") == dict(none, roofline=True)
+    assert legs("--instrumented-only", "--no-cpu-baseline") == dict(none, roofline=True)
+    assert legs("--instrumented-only") == dict(none, roofline=True, cpu_baseline=True)

@@ -10,7 +10,7 @@
 #   suite          the whole -m gpu suite with durations, measured regression values written to the tag directory
 #   pytest         python -m pytest $APE_PYTEST_ARGS -m gpu (+ -k expression in $APE_K), measured pins written to the tag directory
 #   smoke          __graft_entry__.smoke()
-#   bench          the driver's default bench (cpu_baseline + parity) -> bench_default.json
+#   bench          the full bench (--full: value_f16, roofline, cpu_baseline + parity) -> bench_default.json
 #   benches        the other configurations / flavours (no CPU baseline)
 #   profile        tools/gpu_profile.sh (rocprofv3 kernel stats: instrumented pass alone + pipelined graph run)
 #   pmc            tools/gpu_pmc.sh (separate FETCH_SIZE / WRITE_SIZE / SQ passes) + summary
@@ -22,7 +22,7 @@ TAG=$1; shift
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 O=gpurun_out/$TAG
 mkdir -p $O
-b() { name=$1; shift; timeout 400 python bench.py --no-cpu-baseline "$@" 2> $O/bench_$name.err | tail -1 > $O/bench_$name.json; cut -c1-200 $O/bench_$name.json; tail -2 $O/bench_$name.err | cut -c1-200; }
+b() { name=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline "$@" 2> $O/bench_$name.err | tail -1 > $O/bench_$name.json; cut -c1-200 $O/bench_$name.json; tail -2 $O/bench_$name.err | cut -c1-200; }
 for recipe in "$@"; do
   echo "=== $recipe"
   case $recipe in
@@ -52,7 +52,7 @@ PY
     suite) APE_WRITE_PINS=$O timeout 1700 python -m pytest tests -q -s -m gpu --durations=40 2>&1 | grep -v Warning > $O/pytest_gpu.log; tail -50 $O/pytest_gpu.log | cut -c1-200 ;;
     pytest) APE_WRITE_PINS=$O timeout ${APE_PYTEST_TIMEOUT:-1700} python -m pytest ${APE_PYTEST_ARGS:-tests} -q -s -m gpu ${APE_K:+-k "$APE_K"} --durations=15 2>&1 | grep -v Warning > $O/pytest.log; grep -E "passed|failed|error" $O/pytest.log | tail -5 | cut -c1-300; grep -E "^FAILED|^ERROR|assert|Error" $O/pytest.log | head -20 | cut -c1-300 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -5 | tee $O/smoke.log ;;
-    bench) timeout 900 python bench.py ${APE_BENCH_ARGS} 2> $O/bench_default.err | tail -1 > $O/bench_default.json; cut -c1-300 $O/bench_default.json; python tools/bench_digest.py $O/bench_default.json | tee $O/bench_default_digest.txt ;;
+    bench) timeout 900 python bench.py --full ${APE_BENCH_ARGS} 2> $O/bench_default.err | tail -1 > $O/bench_default.json; cut -c1-300 $O/bench_default.json; python tools/bench_digest.py $O/bench_default.json | tee $O/bench_default_digest.txt ;;
     benches)
       b f16 --dtype f16; b input_uint8 --input uint8; b lvis1203_top300 --classes 1203 --size L_D; b stream_coco --stream coco
       b 1536_semantic --size L_D_1536 --semantic --steps 30; b one_image_per_step --images-per-step 1; b L_A --size L_A
@@ -60,7 +60,7 @@ PY
       # the N > 1 code path end to end on a 1-GPU box: two ranks SHARE the device (gloo: RCCL refuses two ranks on one GPU) -- mask format
       # "both", lagged all-gather of records + run lengths, per-rank rates, the same-process N = 1 reference and efficiency_vs_n1.  The
       # throughput of such a run means nothing; that every field is produced does
-      APE_BENCH_SHARE_GPU=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --backend gloo --steps 10 --warmup 2 --solo-steps 6 --no-cpu-baseline 2> $O/bench_n2_shared_gpu_gloo.err | tail -1 > $O/bench_n2_shared_gpu_gloo.json; cut -c1-200 $O/bench_n2_shared_gpu_gloo.json; tail -2 $O/bench_n2_shared_gpu_gloo.err | cut -c1-200 ;;
+      APE_BENCH_SHARE_GPU=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --backend gloo --steps 10 --warmup 2 --full --solo-steps 6 --no-cpu-baseline 2> $O/bench_n2_shared_gpu_gloo.err | tail -1 > $O/bench_n2_shared_gpu_gloo.json; cut -c1-200 $O/bench_n2_shared_gpu_gloo.json; tail -2 $O/bench_n2_shared_gpu_gloo.err | cut -c1-200 ;;
     benches_wide)   # the widened model families: APE on ViT-e, EVA-01 MIM ViT-g (1024^2 / 1536^2), EVA-01-CLIP ViT-g
       b E_D --size E_D --steps 20 --warmup 3 --no-second-flavour; b V_A --size V_A --steps 20 --warmup 3 --no-second-flavour
       b V_A_1536 --size V_A_1536 --steps 10 --warmup 2 --no-second-flavour; b G_A --size G_A --steps 10 --warmup 2 --no-second-flavour ;;
@@ -83,7 +83,7 @@ PY
         python - <<PY | tee -a $O/drivercmd_trace.txt
 import json
 d = json.loads(open("$O/drivercmd_$r.json").read())
-print("run $r: value", round(d["value"], 2), "ms/step", round(d["ms_per_step"], 3), "f16", round(d.get("value_f16") or 0, 2), "frac", round(d["roofline"]["frac"], 4), "avg_us", round(d["roofline"]["avg_launch_us"], 2))
+print("run $r: value", round(d["value"], 2), "ms/step", round(d["ms_per_step"], 3))    # a plain run: no value_f16, no roofline
 t = d.get("step_trace") or {}
 print("  warmup_ms", t.get("warmup_ms")); print("  timed_ms ", t.get("timed_ms"))
 t = d.get("step_trace_f16") or {}
