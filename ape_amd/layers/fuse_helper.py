@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..packing import attach_cache, f32, pack_matrix
+from ..packing import attach_cache, f32, ln_params, pack_matrix
 
 
 class BiMultiHeadAttention(nn.Module):
@@ -70,8 +70,7 @@ class BiAttentionBlock(nn.Module):
             a = self.attn
             nh, hd, vd = a.num_heads, a.head_dim, a.v_dim
             return dict(
-                lnv=(f32(self.layer_norm_v.weight), f32(self.layer_norm_v.bias), self.layer_norm_v.eps),
-                lnl=(f32(self.layer_norm_l.weight), f32(self.layer_norm_l.bias), self.layer_norm_l.eps),
+                lnv=ln_params(self.layer_norm_v), lnl=ln_params(self.layer_norm_l),
                 wl=f32(a.l_proj.weight), bl=f32(a.l_proj.bias), wvl=f32(a.values_l_proj.weight), bvl=f32(a.values_l_proj.bias),
                 wov=f32(a.out_v_proj.weight), bov=f32(a.out_v_proj.bias), wol=f32(a.out_l_proj.weight), bol=f32(a.out_l_proj.bias),
                 wv=f32(a.v_proj.weight).view(nh, hd, vd), bv=f32(a.v_proj.bias).view(nh, hd),

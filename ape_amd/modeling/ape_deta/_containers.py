@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...packing import attach_cache, f32, pack_matrix, permute_ffn_w2
+from ...packing import attach_cache, f32, ln_params, pack_matrix, permute_ffn_w2
 
 
 class FFN(nn.Module):
@@ -118,8 +118,7 @@ class TransformerLayer(nn.Module):
         self.pre_norm = False
 
     def norm_params(self, i):
-        n = self.norms[i]
-        return f32(n.weight), f32(n.bias), n.eps
+        return ln_params(self.norms[i])
 
 
 class ConvNormAct(nn.Module):

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from ... import ops
 from ...layers import MultiScaleDeformableAttention
-from ...packing import attach_cache, f32, pack_matrix, round_up
+from ...packing import attach_cache, f32, ln_params, pack_matrix, round_up
 from ...stagetap import forcing, tap
 from . import geometry as G
 from ._containers import FFN, SelfAttention, TransformerLayer
@@ -63,7 +63,7 @@ class DeformableDetrTransformerEncoderVL(nn.Module):
                     l = tap(stages, f"enc{i}_fused_l", l)
                 x = tap(stages, f"enc{i}_out", x)
         if self.post_norm_layer is not None:
-            x = ops.layernorm(x, f32(self.post_norm_layer.weight), f32(self.post_norm_layer.bias), self.post_norm_layer.eps, out_dtype=dt)
+            x = ops.layernorm(x, *ln_params(self.post_norm_layer), out_dtype=dt)
         return x, l
 
 
@@ -185,11 +185,11 @@ class DeformableDetrTransformerVL(nn.Module):
             ce, cea = dec.class_embed[nd], (dec.class_embed_ambiguous[0] if amb else dec.class_embed[nd])
             return dict(
                 wenc=pack_matrix(self.enc_output.weight, dt), benc=f32(self.enc_output.bias),
-                nenc=(f32(self.enc_output_norm.weight), f32(self.enc_output_norm.bias), self.enc_output_norm.eps),
+                nenc=ln_params(self.enc_output_norm),
                 wpos=pack_matrix(self.pos_trans.weight, dt), bpos=f32(self.pos_trans.bias),
-                npos=(f32(self.pos_trans_norm.weight), f32(self.pos_trans_norm.bias), self.pos_trans_norm.eps),
+                npos=ln_params(self.pos_trans_norm),
                 wpix=pack_matrix(self.pix_trans.weight, dt), bpix=f32(self.pix_trans.bias),
-                npix=(f32(self.pix_trans_norm.weight), f32(self.pix_trans_norm.bias), self.pix_trans_norm.eps),
+                npix=ln_params(self.pix_trans_norm),
                 # two-stage heads: main + ambiguous copies share their input, so their first layers are one GEMM
                 w1=pack_matrix(torch.cat([be.layers[0].weight, bea.layers[0].weight], 0), dt),
                 b1=torch.cat([be.layers[0].bias, bea.layers[0].bias]).detach().float().contiguous(),

@@ -22,9 +22,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ...packing import attach_cache, f32, pack_matrix, round_up
+from ...packing import attach_cache, ln_params, pack_matrix, round_up
 from ...stagetap import tap
-from .vit_eva_clip import Backbone, LastLevelMaxPool, PatchEmbed, SimpleFeaturePyramid, padded_head_dim, window_major_order  # noqa: F401
+from .simple_feature_pyramid import LastLevelMaxPool, SimpleFeaturePyramid  # noqa: F401
+from .vit_common import ViTBase, fork_vt_then_qk, pack_padded_up, pad_heads, padded_head_dim, window_major_order
 
 __all__ = ["ViT", "SimpleFeaturePyramid"]
 
@@ -150,15 +151,7 @@ class Block(nn.Module):
             E, nh = wq.shape[1], a.num_heads
             hd = E // nh
             hdp = padded_head_dim(hd)
-            dev = wq.device
-
-            def pad_heads(w):                      # [nh * hd, ...] -> [nh * hdp, ...], zero rows behind every head
-                if hdp == hd:
-                    return w.contiguous()
-                out = torch.zeros((nh, hdp) + tuple(w.shape[1:]), dtype=torch.float32, device=dev)
-                out[:, :hd] = w.reshape((nh, hd) + tuple(w.shape[1:]))
-                return out.reshape((nh * hdp,) + tuple(w.shape[1:]))
-
+            pad = partial(pad_heads, nh=nh, hd=hd, hdp=hdp)
             wproj, bproj = a.proj.weight.detach().float(), a.proj.bias.detach().float()
             w2, b2 = m.fc2.weight.detach().float(), m.fc2.bias.detach().float()
             if self.beit_like_gamma:               # x + gamma * f(x) (vit_eva.py:296-298): the layer scale folds into f's last linear
@@ -166,21 +159,14 @@ class Block(nn.Module):
                 wproj, bproj = wproj * g1[:, None], bproj * g1
                 w2, b2 = w2 * g2[:, None], b2 * g2
             if hdp != hd:                          # zero COLUMNS of the out projection where the attention output is padding
-                wproj = pad_heads(wproj.t().contiguous()).t().contiguous()
-            hid = m.fc1.weight.shape[0]
-            hid_pad = round_up(hid, 64)
-            w1 = torch.zeros((hid_pad, E), dtype=torch.float32, device=dev)     # zero rows: gelu(0) = 0 exactly in the K padding
-            w1[:hid] = m.fc1.weight.detach().float()
-            b1 = torch.zeros((hid_pad,), dtype=torch.float32, device=dev)
-            b1[:hid] = m.fc1.bias.detach().float()
+                wproj = pad(wproj.t().contiguous()).t().contiguous()
+            w1, b1, _, hid_pad = pack_padded_up(m.fc1, dt)
             P = dict(
                 hd=hd, hdp=hdp, Ep=nh * hdp,
-                wqk=pack_matrix(torch.cat([pad_heads(wq), pad_heads(wk)], 0), dt), bqk=torch.cat([pad_heads(bq), pad_heads(bk)]).contiguous(),
-                wv=pack_matrix(pad_heads(wv), dt), bv=pad_heads(bv).contiguous(),
-                wproj=pack_matrix(wproj, dt), bproj=bproj.contiguous(),
-                n1=(f32(self.norm1.weight), f32(self.norm1.bias), self.norm1.eps),
-                n2=(f32(self.norm2.weight), f32(self.norm2.bias), self.norm2.eps),
-                w1=pack_matrix(w1, dt), b1=b1, hid_pad=hid_pad, w2=pack_matrix(w2, dt, kpad=64), b2=b2.contiguous())
+                wqk=pack_matrix(torch.cat([pad(wq), pad(wk)], 0), dt), bqk=torch.cat([pad(bq), pad(bk)]).contiguous(),
+                wv=pack_matrix(pad(wv), dt), bv=pad(bv).contiguous(),
+                wproj=pack_matrix(wproj, dt), bproj=bproj.contiguous(), n1=ln_params(self.norm1), n2=ln_params(self.norm2),
+                w1=w1, b1=b1, hid_pad=hid_pad, w2=pack_matrix(w2, dt, kpad=64), b2=b2.contiguous())
             if a.use_rel_pos:
                 rh, rw = resized_rel_pos(a.rel_pos_h, group, a.interp_type), resized_rel_pos(a.rel_pos_w, group, a.interp_type)
                 nr = rh.shape[0] + rw.shape[0]
@@ -197,8 +183,7 @@ class Block(nn.Module):
         a = self.attn
         nh, hd, hdp, Ep = a.num_heads, P["hd"], P["hdp"], P["Ep"]
         xn = ops.layernorm(x, P["n1"][0], P["n1"][1], P["n1"][2], out_dtype=dt)
-        vjob = ops.fork(lambda: ops.gemm(xn, P["wv"], P["bv"], trans_out=True, out=vt_buf))
-        qk = ops.gemm(xn, P["wqk"], P["bqk"])
+        qk, vjob = fork_vt_then_qk(xn, P, vt_buf)
         batch, n = (nwin, ntok_win) if self.window_size > 0 else (images, x.shape[0] // images)
         if a.use_rel_pos:
             # rows (token, q head | k head): the k rows of this product are unused (one GEMM over the q|k buffer as it lies in HBM)
@@ -217,7 +202,7 @@ class Block(nn.Module):
         return ops.gemm(hbuf, P["w2"], P["b2"], residual=x, out_dtype=dt if last else torch.float32)
 
 
-class ViT(Backbone):
+class ViT(ViTBase):
     def __init__(self, img_size=1024, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True,
                  drop_path_rate=0.0, norm_layer=partial(nn.LayerNorm, eps=1e-6), act_layer=nn.GELU, use_abs_pos=True, use_rel_pos=False,
                  rel_pos_zero_init=True, window_size=0, window_block_indexes=(), residual_block_indexes=(), use_act_checkpoint=False,
@@ -227,11 +212,7 @@ class ViT(Backbone):
         assert use_abs_pos and patch_size == 16 and len(residual_block_indexes) == 0, \
             "ape_amd vit_eva: absolute position embedding, 16 x 16 patches, no convolutional residual blocks (every APE config)"
         assert window_size > 0 and (img_size // patch_size) % window_size == 0, "token grid must be a multiple of the window size"
-        self.pretrain_use_cls_token = pretrain_use_cls_token
-        self.img_size, self.patch_size, self.embed_dim, self.window_size = img_size, patch_size, embed_dim, window_size
-        self.patch_embed = PatchEmbed(in_chans=in_chans, embed_dim=embed_dim)
-        num_patches = (pretrain_img_size // patch_size) ** 2
-        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + (1 if pretrain_use_cls_token else 0), embed_dim))
+        self._init_embed(img_size, patch_size, in_chans, embed_dim, window_size, pretrain_img_size, pretrain_use_cls_token)
         if beit_like_qkv_bias:
             qkv_bias = False                                                                # vit_eva.py:399-400
         hw = img_size // patch_size
@@ -240,12 +221,7 @@ class ViT(Backbone):
                   use_rel_pos=use_rel_pos, rel_pos_zero_init=rel_pos_zero_init, window_size=window_size if i in window_block_indexes else 0,
                   use_residual_block=False, input_size=(hw, hw), beit_like_qkv_bias=beit_like_qkv_bias, beit_like_gamma=beit_like_gamma,
                   interp_type=interp_type) for i in range(depth)])
-        self._out_feature_channels = {out_feature: embed_dim}
-        self._out_feature_strides = {out_feature: patch_size}
-        self._out_features = [out_feature]
-        nn.init.trunc_normal_(self.pos_embed, std=0.02)
-        self.compute_dtype = torch.bfloat16
-        attach_cache(self)
+        self._init_tail(out_feature)
 
     def token_order(self, hw):
         """(tok2raster, raster2tok) of the feature this ViT hands to the pyramid: window-major order"""
@@ -258,17 +234,8 @@ class ViT(Backbone):
             dev = self.pos_embed.device
             t2r, r2t = window_major_order(hw, hw, ws)
             t2r, r2t = t2r.to(dev), r2t.to(dev)
-            pos = self.pos_embed.detach().float()                      # get_abs_pos: drop cls, bicubic resize to the token grid
-            if self.pretrain_use_cls_token:
-                pos = pos[:, 1:]
-            size = int(math.sqrt(pos.shape[1]))
-            if size != hw:
-                pos = F.interpolate(pos.reshape(1, size, size, -1).permute(0, 3, 1, 2), size=(hw, hw), mode="bicubic",
-                                    align_corners=False).permute(0, 2, 3, 1)
-            pos = pos.reshape(hw * hw, -1)[t2r.long()].contiguous()
-            w = self.patch_embed.proj.weight
             j = torch.arange(ws * ws, device=dev)
-            return dict(hw=hw, t2r=t2r, r2t=r2t, pos=pos, wpe=pack_matrix(w.reshape(w.shape[0], -1), dt), bpe=f32(self.patch_embed.proj.bias),
+            return dict(self._packed_embed(dt, t2r), t2r=t2r, r2t=r2t,
                         # a token's (row, col) inside its attention group: the window / the whole grid (window-major token order)
                         coords_win=((j // ws).to(torch.int32).contiguous(), (j % ws).to(torch.int32).contiguous()),
                         coords_glb=((t2r // hw).to(torch.int32).contiguous(), (t2r % hw).to(torch.int32).contiguous()))
@@ -279,22 +246,8 @@ class ViT(Backbone):
         WINDOW-MAJOR token order per image (same contract as vit_eva_clip.ViT.forward_tokens)"""
         dt = self.compute_dtype
         P = self.packed(dt)
-        hw = P["hw"]
-        n = hw * hw
-        images = list(image) if isinstance(image, (list, tuple)) else [image]
-        B = len(images)
-        if B == 1:
-            patches = ops.patchify(images[0], P["t2r"], hw, hw, mean, std, out_dtype=dt)
-            pos = P["pos"]
-        else:
-            patches = torch.empty((B * n, 768), dtype=dt, device=images[0].device)
-            for b, im in enumerate(images):
-                ops.patchify(im, P["t2r"], hw, hw, mean, std, out_dtype=dt, out=patches[b * n:(b + 1) * n])
-            if ("pos", B) not in P:
-                P[("pos", B)] = P["pos"].repeat(B, 1).contiguous()
-            pos = P[("pos", B)]
-        x = tap(stages, "vit_embed", ops.gemm(patches, P["wpe"], P["bpe"], residual=pos, out_dtype=torch.float32))
-        nwin = (hw // self.window_size) ** 2 * B
+        x, B, n = self.embed_images(P, P["t2r"], image, mean, std, stages)
+        nwin = (P["hw"] // self.window_size) ** 2 * B
         Ep = self.blocks[0].attn.num_heads * padded_head_dim(self.embed_dim // self.blocks[0].attn.num_heads)
         vt_buf = ops.zeros((Ep, round_up(B * n, 64)), dt, x.device)
         for i, blk in enumerate(self.blocks):
@@ -302,12 +255,3 @@ class ViT(Backbone):
             x = blk.forward_tokens(x, dt, coords, nwin, self.window_size ** 2, vt_buf, last=(i == len(self.blocks) - 1), images=B)
             x = tap(stages, f"vit_blk{i}", x)
         return x
-
-    def forward(self, x):
-        """reference signature: normalised, padded NCHW batch -> {"last_feat": [B, E, h/16, w/16]}"""
-        outs = []
-        P = self.packed(self.compute_dtype)
-        for b in range(x.shape[0]):
-            t = self.forward_tokens(x[b].float().contiguous())
-            outs.append(t[P["r2t"].long()].float().reshape(P["hw"], P["hw"], -1).permute(2, 0, 1))
-        return {self._out_features[0]: torch.stack(outs)}

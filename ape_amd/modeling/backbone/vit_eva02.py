@@ -12,19 +12,18 @@ MI355X mapping.  The residual stream stays raster-ordered [4096, E]; a windowed 
 window-major order (25 windows x 196 slots, stored at a stride of 200 rows so that every window starts 16-byte aligned
 in V^T), padding / slack slots reading an all-zero row -- so the q|k GEMM (RoPE in its epilogue) and the V^T GEMM give
 exactly q = rope(q_bias), k = 0, v = v_bias there -- runs the strided flash-attention kernel and gathers the real
-tokens back.  SimpleFeaturePyramid is the one of vit_eva_clip.py (identical in the reference, vit_eva02.py:637-804).
+tokens back.  SimpleFeaturePyramid is the shared one of simple_feature_pyramid.py (identical in the reference, vit_eva02.py:637-804).
 """
-import math
 from functools import partial
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ... import ops
-from ...packing import attach_cache, f32, pack_matrix, round_up
+from ...packing import attach_cache, f32, ln_params, pack_matrix, round_up
 from ...stagetap import tap
-from .vit_eva_clip import Backbone, PatchEmbed, SimpleFeaturePyramid, VisionRotaryEmbeddingFast  # noqa: F401
+from .simple_feature_pyramid import SimpleFeaturePyramid  # noqa: F401
+from .vit_common import ViTBase, VisionRotaryEmbeddingFast, pack_swiglu_up
 
 __all__ = ["ViT", "SimpleFeaturePyramid"]
 
@@ -92,29 +91,22 @@ class Block(nn.Module):
             wq, wk, wv = (w.detach().float() for w in a.qkv_weights())
             E = wq.shape[0]
             zeros = torch.zeros(E, dtype=torch.float32, device=wq.device)
-            hid = m.hidden_features
-            hid_pad = round_up(hid, 64)
             if isinstance(m, xops_SwiGLU):          # _ordered_params (:107-149): w1 = first half of w12, w2 = second half
                 w1, w2 = m.w12.weight.detach().float().chunk(2, dim=0)
                 b1, b2 = m.w12.bias.detach().float().chunk(2, dim=0)
             else:
-                w1, w2, b1, b2 = m.w1.weight.detach().float(), m.w2.weight.detach().float(), m.w1.bias.detach().float(), m.w2.bias.detach().float()
-            w12 = torch.zeros((2 * hid_pad, E), dtype=torch.float32, device=wq.device)     # (gate, up) rows interleaved
-            b12 = torch.zeros((2 * hid_pad,), dtype=torch.float32, device=wq.device)
-            w12[0:2 * hid:2], w12[1:2 * hid:2] = w1, w2
-            b12[0:2 * hid:2], b12[1:2 * hid:2] = b1, b2
+                w1, w2, b1, b2 = m.w1.weight, m.w2.weight, m.w1.bias, m.w2.bias
+            w12, b12, hid, hid_pad = pack_swiglu_up(w1, b1, w2, b2, dt)
             d = dict(
                 wqk=pack_matrix(torch.cat([wq, wk], 0), dt),
                 bqk=torch.cat([f32(a.q_bias) if a.q_bias is not None else zeros, zeros]).contiguous(),
                 wv=pack_matrix(wv, dt), bv=f32(a.v_bias) if a.v_bias is not None else zeros,
                 wproj=pack_matrix(a.proj.weight, dt), bproj=f32(a.proj.bias),
-                w12=pack_matrix(w12, dt), b12=b12, hid=hid, hid_pad=hid_pad,
-                w3=pack_matrix(m.w3.weight, dt, kpad=64), b3=f32(m.w3.bias),
-                n1=(f32(self.norm1.weight), f32(self.norm1.bias), self.norm1.eps),
-                n2=(f32(self.norm2.weight), f32(self.norm2.bias), self.norm2.eps),
+                w12=w12, b12=b12, hid=hid, hid_pad=hid_pad,
+                w3=pack_matrix(m.w3.weight, dt, kpad=64), b3=f32(m.w3.bias), n1=ln_params(self.norm1), n2=ln_params(self.norm2),
             )
             if isinstance(m, SwiGLU):
-                d["nffn"] = (f32(m.ffn_ln.weight), f32(m.ffn_ln.bias), m.ffn_ln.eps)
+                d["nffn"] = ln_params(m.ffn_ln)
             return d
         return self._pack.get(self, dt, build)
 
@@ -147,7 +139,7 @@ class Block(nn.Module):
         return ops.gemm(h, P["w3"], P["b3"], residual=x, out_dtype=dt if last else torch.float32)
 
 
-class ViT(Backbone):
+class ViT(ViTBase):
     def __init__(self, img_size=1024, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4 * 2 / 3,
                  qkv_bias=True, drop_path_rate=0.0, norm_layer=partial(nn.LayerNorm, eps=1e-6), act_layer=nn.GELU,
                  use_abs_pos=True, use_rel_pos=False, rope=True, pt_hw_seq_len=16, intp_freq=True, window_size=0,
@@ -158,11 +150,7 @@ class ViT(Backbone):
         assert rope and use_abs_pos and patch_size == 16 and len(residual_block_indexes) == 0, \
             "ape_amd vit_eva02.ViT: the rope + abs-pos configuration without residual conv blocks is implemented"
         assert (embed_dim // num_heads) in (32, 64), "the HIP attention kernel handles head_dim 32 / 64"
-        self.pretrain_use_cls_token = pretrain_use_cls_token
-        self.img_size, self.patch_size, self.embed_dim, self.window_size = img_size, patch_size, embed_dim, window_size
-        self.patch_embed = PatchEmbed(in_chans=in_chans, embed_dim=embed_dim)
-        num_patches = (pretrain_img_size // patch_size) ** 2
-        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + (1 if pretrain_use_cls_token else 0), embed_dim))
+        self._init_embed(img_size, patch_size, in_chans, embed_dim, window_size, pretrain_img_size, pretrain_use_cls_token)
         half_head_dim = embed_dim // num_heads // 2
         hw = img_size // patch_size
         self.rope_win = VisionRotaryEmbeddingFast(half_head_dim, pt_seq_len=pt_hw_seq_len, ft_seq_len=window_size if intp_freq else None)
@@ -171,12 +159,7 @@ class ViT(Backbone):
             Block(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer, window_size if i in window_block_indexes else 0,
                   self.rope_win if i in window_block_indexes else self.rope_glb, subln, swiglu, naiveswiglu)
             for i in range(depth)])
-        self._out_feature_channels = {out_feature: embed_dim}
-        self._out_feature_strides = {out_feature: patch_size}
-        self._out_features = [out_feature]
-        nn.init.trunc_normal_(self.pos_embed, std=0.02)
-        self.compute_dtype = torch.bfloat16
-        attach_cache(self)
+        self._init_tail(out_feature)
 
     def token_order(self, hw):
         """(tok2raster, raster2tok) of the feature this ViT hands to the pyramid: raster order"""
@@ -188,16 +171,7 @@ class ViT(Backbone):
             hw = self.img_size // self.patch_size
             dev = self.pos_embed.device
             n = hw * hw
-            pos = self.pos_embed.detach().float()
-            if self.pretrain_use_cls_token:
-                pos = pos[:, 1:]
-            size = int(math.sqrt(pos.shape[1]))
-            if size != hw:                             # get_abs_pos (utils_eva02.py:158-187)
-                pos = F.interpolate(pos.reshape(1, size, size, -1).permute(0, 3, 1, 2), size=(hw, hw), mode="bicubic",
-                                    align_corners=False).permute(0, 2, 3, 1)
-            w = self.patch_embed.proj.weight
-            d = dict(hw=hw, ident=torch.arange(n, dtype=torch.int32, device=dev), pos=pos.reshape(n, -1).contiguous(),
-                     wpe=pack_matrix(w.reshape(w.shape[0], -1), dt), bpe=f32(self.patch_embed.proj.bias),
+            d = dict(self._packed_embed(dt), ident=torch.arange(n, dtype=torch.int32, device=dev),
                      rope_glb=(f32(self.rope_glb.freqs_cos), f32(self.rope_glb.freqs_sin), n), win=None)
             ws = self.window_size
             if ws > 0:
@@ -224,12 +198,9 @@ class ViT(Backbone):
         """image [3,h,w] fp32 (h,w <= img_size) -> last feature [N, E] in the compute dtype, RASTER token order"""
         dt = self.compute_dtype
         P = self.packed(dt)
-        hw = P["hw"]
-        n = hw * hw
         if isinstance(image, (list, tuple)):
             return torch.cat([self.forward_tokens(im, mean, std) for im in image], 0)
-        patches = ops.patchify(image, P["ident"], hw, hw, mean, std, out_dtype=dt)
-        x = tap(stages, "vit_embed", ops.gemm(patches, P["wpe"], P["bpe"], residual=P["pos"], out_dtype=torch.float32))
+        x, _, n = self.embed_images(P, P["ident"], image, mean, std, stages)
         xn_buf = torch.zeros((n + 1, self.embed_dim), dtype=dt, device=x.device)
         rows = n if P["win"] is None else max(n, P["win"]["nwin"] * P["win"]["stride"])
         # the attention kernel reads V^T in 64-column tiles from every window's first column: the last window's last tile ends
@@ -243,12 +214,3 @@ class ViT(Backbone):
                 x = blk.forward_tokens(x, dt, P["rope_glb"], None, xn_buf, vt_buf, last)
             x = tap(stages, f"vit_blk{i}", x)
         return x
-
-    def forward(self, x):
-        """reference signature: normalised, padded NCHW batch -> {"last_feat": [B, E, h/16, w/16]}"""
-        outs = []
-        hw = self.img_size // self.patch_size
-        for b in range(x.shape[0]):
-            t = self.forward_tokens(x[b].float().contiguous())
-            outs.append(t.float().reshape(hw, hw, -1).permute(2, 0, 1))
-        return {self._out_features[0]: torch.stack(outs)}

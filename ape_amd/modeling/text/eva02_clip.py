@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...packing import attach_cache, f32, pack_matrix, round_up
+from ...packing import attach_cache, f32, ln_params, pack_matrix, round_up
 
 # text_cfg / embed_dim of the reference's model_configs/*.json (head width 64 everywhere; nn.GELU; LayerNorm eps 1e-5)
 TEXT_CONFIGS = {
@@ -63,8 +63,7 @@ class ResidualAttentionBlock(nn.Module):
                 wo=pack_matrix(a.out_proj.weight, dt), bo=f32(a.out_proj.bias),
                 wfc=pack_matrix(self.mlp.c_fc.weight, dt), bfc=f32(self.mlp.c_fc.bias),
                 wpr=pack_matrix(self.mlp.c_proj.weight, dt), bpr=f32(self.mlp.c_proj.bias),
-                n1=(f32(self.ln_1.weight), f32(self.ln_1.bias), self.ln_1.eps),
-                n2=(f32(self.ln_2.weight), f32(self.ln_2.bias), self.ln_2.eps))
+                n1=ln_params(self.ln_1), n2=ln_params(self.ln_2))
         return self._pack.get(self, dt, build)
 
     def forward_tokens(self, x, dt, batch, length, stride, vt_buf):
@@ -117,7 +116,7 @@ class TextTransformer(nn.Module):
         def build(dt):
             return dict(emb=self.token_embedding.weight.detach().to(dt).contiguous(),
                         pos=self.positional_embedding.detach().to(dt).contiguous(),
-                        nf=(f32(self.ln_final.weight), f32(self.ln_final.bias), self.ln_final.eps),
+                        nf=ln_params(self.ln_final),
                         wproj=pack_matrix(self.text_projection.detach().t(), dt))
         return self._pack.get(self, dt, build)
 

@@ -40,6 +40,11 @@ def f32(t):
     return None if t is None else t.detach().float().contiguous()
 
 
+def ln_params(norm):
+    """(weight, bias, eps) of a LayerNorm as ops.layernorm takes them"""
+    return f32(norm.weight), f32(norm.bias), norm.eps
+
+
 class PackCache:
     """per-module cache of packed tensors, keyed by (compute dtype, device); dropped when weights change"""
 
