@@ -162,6 +162,9 @@ SIGNATURES = {
     "ape_hip_rle_workspace_words": (c_int, [c_int, c_int, c_int, c_int]),
     "ape_hip_rle_encode": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "ape_hip_rle_to_string": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "ape_hip_label_hist_lds_bins": (c_int, []),
+    "ape_hip_label_pair_hist": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p]),
 }
 
 _lib = None

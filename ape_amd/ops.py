@@ -849,6 +849,47 @@ def argmax_labels(x, class0=None, out=None):
     return out
 
 
+_LABEL_BYTES = {torch.uint8: 1, torch.int16: 2, torch.int32: 4}
+
+
+def label_hist_lds_bins():
+    """the largest table (na * nb bins) `label_pair_hist` counts in LDS on the current device; larger tables are counted in global memory"""
+    bins = _lib.load().ape_hip_label_hist_lds_bins()
+    if bins < 0:
+        _lib.check(bins, "ape_hip_label_hist_lds_bins")
+    return bins
+
+
+def label_pair_hist(a, b, na, nb, a_ignore=None, b_ignore=None, out=None, rejected=None):
+    """joint histogram of two label maps of equal numel (uint8 / int16 / int32, contiguous): -> (hist int64 [na, nb], rejected int64 [1]).
+    A value equal to a_ignore counts as na - 1 (b_ignore: nb - 1); a pair with a outside [0, na) or b outside [0, nb) is counted in
+    `rejected` and in no bin.  out / rejected given: the call ADDS to them (one resident matrix over a dataset); otherwise zeroed ones
+    are allocated.  int64 / bool maps are not reinterpreted: TypeError."""
+    _dev(a, b, out, rejected)
+    for t, name in ((a, "a"), (b, "b")):
+        if t.dtype not in _LABEL_BYTES:
+            raise TypeError(f"ape_amd.ops.label_pair_hist: {name} is {t.dtype}; label maps are uint8, int16 or int32")
+        if not t.is_contiguous():
+            raise ValueError(f"ape_amd.ops.label_pair_hist: {name} must be contiguous")
+    if a.numel() != b.numel():
+        raise ValueError(f"ape_amd.ops.label_pair_hist: a has {a.numel()} labels, b has {b.numel()}")
+    na, nb = int(na), int(nb)
+    if na < 1 or nb < 1:
+        raise ValueError("ape_amd.ops.label_pair_hist: na and nb must be at least 1")
+    if out is None:
+        out = torch.zeros((na, nb), dtype=torch.int64, device=a.device)
+    if rejected is None:
+        rejected = torch.zeros((1,), dtype=torch.int64, device=a.device)
+    if (out.dtype != torch.int64 or rejected.dtype != torch.int64 or tuple(out.shape) != (na, nb) or rejected.numel() != 1
+            or not out.is_contiguous()):
+        raise ValueError("ape_amd.ops.label_pair_hist: out / rejected must be contiguous int64 [na, nb] / [1]")
+    rc = _lib.load().ape_hip_label_pair_hist(_p(a), _LABEL_BYTES[a.dtype], _p(b), _LABEL_BYTES[b.dtype], a.numel(), na, nb,
+                                             -1 if a_ignore is None else int(a_ignore), -1 if b_ignore is None else int(b_ignore),
+                                             _p(out), _p(rejected), _stream())
+    _lib.check(rc, "ape_hip_label_pair_hist")
+    return out, rejected
+
+
 def bilinear_resize(x, height, width):
     """F.interpolate(x[None], (height, width), mode="bilinear", align_corners=False)[0] for fp32 x [C, h, w]
     (rows contiguous; channel / row strides free)."""

@@ -560,6 +560,21 @@ int ape_hip_ffn_fused(const void* X, int ldx, const void* W1, int ldw1, const fl
                       const void* residual, int ldr, void* Y, int ldy, int M, int K, int HID, int N, int w2_permuted, int dt,
                       const float* ln_weight, const float* ln_bias, float ln_eps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Joint histogram of two label maps, the primitive of the segmentation scores (ape_amd/evaluation.py): the semantic confusion
+ * matrix is hist[pred class, gt class] (detectron2's SemSegEvaluator), the panoptic segment intersections are
+ * hist[gt segment, pred segment] (panopticapi's pq_compute_single_core).  -- csrc/labelhist.hip
+ * a, b: n labels each, a_bytes / b_bytes = 1 (uint8) | 2 (int16) | 4 (int32).  Per element: a value equal to a_ignore counts as
+ * na - 1 (b_ignore: nb - 1; -1 = no ignore value); then a pair with a outside [0, na) or b outside [0, nb) adds 1 to *rejected,
+ * every other pair adds 1 to hist[a][b].  hist [na, nb] row-major and rejected [1] are int64 and are ADDED to (one resident
+ * matrix per dataset).  No workspace, no host synchronisation; exact for any order of arrival.  n == 0 is a no-op.
+ * Tables of up to ape_hip_label_hist_lds_bins() bins (the 32-bit counters that fit the LDS one workgroup may allocate on the
+ * current device; negative without a device) are counted in LDS and flushed once per workgroup, larger ones in global memory.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_label_hist_lds_bins(void);
+int ape_hip_label_pair_hist(const void* a, int a_bytes, const void* b, int b_bytes, size_t n, int na, int nb, int a_ignore,
+                            int b_ignore, int64_t* hist, int64_t* rejected, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
