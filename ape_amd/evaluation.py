@@ -52,6 +52,36 @@ def rles_from_runs(counts, nruns, size):
             for i in range(counts.shape[0])]
 
 
+def _default_device():
+    return torch.device("cuda" if torch.cuda.is_available() else "cpu")
+
+
+def decode_masks(rles, device=None):
+    """list of COCO RLE dicts {"size": [h, w], "counts": bytes | str | list of run lengths} of ONE size -> uint8 [n, h, w] on the
+    device, the inverse of `encode_masks`: the strings become run lengths on the host (`ops.rle_from_string`), only the runs
+    travel, and `ops.rle_decode` writes the masks.  An uncompressed `counts` list (COCO's other form) is taken as it is."""
+    rles = list(rles)
+    if not rles:
+        raise ValueError("decode_masks: an empty list has no size; build the [0, h, w] tensor yourself")
+    size = [int(v) for v in rles[0]["size"]]
+    runs = []
+    for r in rles:
+        if [int(v) for v in r["size"]] != size:
+            raise ValueError(f"decode_masks: masks of size {list(r['size'])} and {size} in one call")
+        c = r["counts"]
+        if isinstance(c, (bytes, bytearray, str)):
+            runs.append(ops.rle_from_string(c))
+        else:
+            runs.append(torch.as_tensor(c, dtype=torch.int64).reshape(-1).to(torch.int32))
+    cap = max(1, max(int(c.numel()) for c in runs))
+    counts = torch.zeros((len(runs), cap), dtype=torch.int32)
+    for i, c in enumerate(runs):
+        counts[i, : c.numel()] = c
+    nruns = torch.tensor([int(c.numel()) for c in runs], dtype=torch.int32)
+    device = _default_device() if device is None else torch.device(device)
+    return ops.rle_decode(counts.to(device), nruns.to(device), size[0], size[1])
+
+
 def instances_to_coco_json(instances, img_id):
     """d3_evaluation.py:441-493 with the mask encoding on the device"""
     num_instance = len(instances)
@@ -92,27 +122,19 @@ def _iou_matrix(a, b):
     return inter / (area_a[:, None] + area_b[None, :] - inter).clamp_min(1e-300)
 
 
-def box_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
-    """COCO-style box AP of `detections` against `ground_truth` (the protocol of pycocotools' COCOeval that the reference's
-    evaluators run -- ape/evaluation/lvis_evaluation.py / detectron2's COCOEvaluator -- restated: area range "all", no crowd
-    regions, at most `max_dets` detections per (image, CATEGORY) -- COCOeval applies maxDets inside its per-category evaluateImg, so a
-    model top-k of 300 / 500 loses nothing to the default 100 --, IoU thresholds 0.50:0.05:0.95, greedy matching in score order to the
-    unmatched ground truth of the same class with the highest IoU, precision made monotone and sampled at 101 recall points,
-    averaged over thresholds and over the classes that have ground truth).  pycocotools is not installable here: unpinned.
-
-    detections: list (one entry per image) of (boxes [n, 4] XYXY, scores [n], classes [n]);
-    ground_truth: list of (boxes [m, 4] XYXY, classes [m]).  -> dict(AP, AP50, AP75, classes, gt, dets)."""
+def _coco_ap(records, iou_thresholds=None, max_dets=100):
+    """The protocol part of `box_ap` and `mask_ap`: records is a list (one entry per image) of (scores [n], classes [n],
+    gt_classes [m], iou [n, m] float64) on the host, detections in any order.  Greedy matching per (image, class) in score order,
+    the monotone precision envelope and its 101 recall points, averaged over thresholds and over the classes with ground truth."""
     if iou_thresholds is None:
         iou_thresholds = [0.5 + 0.05 * i for i in range(10)]
     T = len(iou_thresholds)
     thr = torch.tensor(iou_thresholds, dtype=torch.float64)
     per_class = {}                      # class -> list of (scores [n], matched [T, n]) per image, and the GT count
     n_gt = {}
-    for (db, ds, dc), (gb, gc) in zip(detections, ground_truth):
-        db, ds, dc = db.detach().cpu().double(), ds.detach().cpu().double(), dc.detach().cpu().long()
-        gb, gc = gb.detach().cpu().double(), gc.detach().cpu().long()
+    for ds, dc, gc, full in records:
         order = torch.argsort(ds, descending=True, stable=True)
-        db, ds, dc = db[order], ds[order], dc[order]
+        ds, dc, full = ds[order], dc[order], full[order]
         for c in set(dc.tolist()) | set(gc.tolist()):
             d_idx, g_idx = (dc == c).nonzero().flatten()[:max_dets], (gc == c).nonzero().flatten()
             n_gt[c] = n_gt.get(c, 0) + int(g_idx.numel())
@@ -120,7 +142,7 @@ def box_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
                 continue
             matched = torch.zeros((T, d_idx.numel()), dtype=torch.bool)
             if g_idx.numel() > 0:
-                iou = _iou_matrix(db[d_idx], gb[g_idx])
+                iou = full[d_idx][:, g_idx]
                 for t in range(T):
                     taken = torch.zeros(g_idx.numel(), dtype=torch.bool)
                     for i in range(d_idx.numel()):                       # detections are in descending score order
@@ -160,6 +182,28 @@ def box_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
     pick = lambda v: float(A[:, min(range(T), key=lambda i: abs(iou_thresholds[i] - v))].mean())   # noqa: E731
     return {"AP": float(A.mean()), "AP50": pick(0.5), "AP75": pick(0.75), "classes": int(A.shape[0]),
             "gt": int(sum(n_gt.values())), "dets": int(sum(e[0].numel() for es in per_class.values() for e in es))}
+
+
+def box_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
+    """COCO-style box AP of `detections` against `ground_truth` (the protocol of pycocotools' COCOeval that the reference's
+    evaluators run -- ape/evaluation/lvis_evaluation.py / detectron2's COCOEvaluator -- restated: area range "all", no crowd
+    regions, at most `max_dets` detections per (image, CATEGORY) -- COCOeval applies maxDets inside its per-category evaluateImg, so a
+    model top-k of 300 / 500 loses nothing to the default 100 --, IoU thresholds 0.50:0.05:0.95, greedy matching in score order to the
+    unmatched ground truth of the same class with the highest IoU, precision made monotone and sampled at 101 recall points,
+    averaged over thresholds and over the classes that have ground truth).  pycocotools is not installable here: unpinned.
+
+    detections: list (one entry per image) of (boxes [n, 4] XYXY, scores [n], classes [n]);
+    ground_truth: list of (boxes [m, 4] XYXY, classes [m]).  -> dict(AP, AP50, AP75, classes, gt, dets)."""
+    records = []
+    for (db, ds, dc), (gb, gc) in zip(detections, ground_truth):
+        db, ds, dc = db.detach().cpu().double(), ds.detach().cpu().double(), dc.detach().cpu().long()
+        gb, gc = gb.detach().cpu().double(), gc.detach().cpu().long()
+        if ds.numel() > 0 and gc.numel() > 0:
+            iou = _iou_matrix(db, gb)
+        else:
+            iou = torch.zeros((ds.numel(), gc.numel()), dtype=torch.float64)
+        records.append((ds, dc, gc, iou))
+    return _coco_ap(records, iou_thresholds, max_dets)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -433,3 +477,92 @@ class PanopticAccumulator:
     def compute(self):
         """{"All" | "Things" | "Stuff": {"PQ", "SQ", "RQ" (x 100), "n"}} over the classes with tp + fp + fn > 0"""
         return panoptic_quality(self.per_class(), self.isthing)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Instance masks.  The IoU matrix of an image's detections against its ground truth is counted on the device by
+# `ops.mask_pair_iou` (csrc/maskiou.hip: one bit pack per side, one popcount contraction); only the [n, m] matrix travels.
+# The protocol that follows is `_coco_ap`, the same code `box_ap` runs.
+# ------------------------------------------------------------------------------------------------------------------
+def _device_masks(masks, device=None):
+    """[n, H, W] masks on the device from a device tensor, a host tensor (uploaded) or a list of RLE dicts (decoded); None for an
+    empty list, which has no size"""
+    if isinstance(masks, (list, tuple)):
+        return decode_masks(masks, device) if len(masks) > 0 else None
+    if masks.dim() != 3:
+        raise ValueError(f"masks must be [n, H, W], got {tuple(masks.shape)}")
+    if not masks.is_cuda:
+        masks = masks.to(_default_device() if device is None else device)
+    return masks.contiguous()
+
+
+class MaskAPAccumulator:
+    """COCO-style mask AP of a dataset: the protocol `box_ap` documents, with mask IoU in place of box IoU.  `update` packs each side
+    of an image once, counts the whole n x m intersection matrix in one launch (`ops.mask_pair_iou`) and keeps only the image's small
+    host record -- scores, classes and the IoU matrix; the per-class greedy matching stays on the host, in `compute`.
+    Out of scope, as for `box_ap`: crowd regions, area ranges (APs / APm / APl), polygon ground truth (there is no rasteriser here)
+    and the LVIS federated protocol.  pycocotools is not a dependency of this package: unpinned."""
+
+    def __init__(self, iou_thresholds=None, max_dets=100, device=None):
+        self.iou_thresholds = None if iou_thresholds is None else [float(t) for t in iou_thresholds]
+        self.max_dets = int(max_dets)
+        self.device = None if device is None else torch.device(device)
+        self.records = []
+
+    def update(self, pred, scores=None, classes=None, gt_masks=None, gt_classes=None):
+        """pred: masks [n, H, W] (uint8 / bool; device tensor, host tensor or list of RLE dicts) with `scores` [n] and `classes` [n],
+        or an `Instances` carrying `pred_masks` or `pred_masks_rle` next to `scores` and `pred_classes`;
+        gt_masks: [m, H, W] in any of the three forms, gt_classes [m]"""
+        if hasattr(pred, "has") and hasattr(pred, "get_fields"):
+            inst = pred
+            if inst.has("pred_masks"):
+                pred = inst.pred_masks
+            elif inst.has("pred_masks_rle"):
+                pred = list(inst.pred_masks_rle)
+            else:
+                raise ValueError("MaskAPAccumulator.update: the instances carry neither pred_masks nor pred_masks_rle")
+            scores = inst.scores if scores is None else scores
+            classes = inst.pred_classes if classes is None else classes
+        if scores is None or classes is None or gt_masks is None or gt_classes is None:
+            raise ValueError("MaskAPAccumulator.update: scores, classes, gt_masks and gt_classes are all needed")
+        ds = torch.as_tensor(scores).detach().cpu().double().reshape(-1)
+        dc = torch.as_tensor(classes).detach().cpu().long().reshape(-1)
+        gc = torch.as_tensor(gt_classes).detach().cpu().long().reshape(-1)
+        n, m = len(pred), len(gt_masks)
+        if ds.numel() != n or dc.numel() != n or gc.numel() != m:
+            raise ValueError(f"MaskAPAccumulator.update: {n} masks with {ds.numel()} scores and {dc.numel()} classes; "
+                             f"{m} ground-truth masks with {gc.numel()} classes")
+        if n == 0 or m == 0:
+            iou = torch.zeros((n, m), dtype=torch.float64)
+        else:
+            a = _device_masks(pred, self.device)
+            b = _device_masks(gt_masks, a.device)
+            if tuple(a.shape[1:]) != tuple(b.shape[1:]):
+                raise ValueError(f"MaskAPAccumulator.update: prediction masks {tuple(a.shape[1:])} vs ground truth {tuple(b.shape[1:])}")
+            iou = ops.mask_pair_iou(a, b)[0].cpu()
+        self.records.append((ds, dc, gc, iou))
+
+    def reduce(self, group=None):
+        """gather every rank's records (torch.distributed.all_gather_object; every rank ends with all of them, in rank order); a
+        no-op in a process without a process group"""
+        if not _distributed():
+            return
+        import torch.distributed as dist
+        parts = [None] * dist.get_world_size(group)
+        dist.all_gather_object(parts, self.records, group=group)
+        self.records = [r for part in parts for r in part]
+
+    def compute(self):
+        """dict(AP, AP50, AP75, classes, gt, dets), the keys of `box_ap`"""
+        return _coco_ap(self.records, self.iou_thresholds, self.max_dets)
+
+
+def mask_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
+    """COCO-style mask AP (see `MaskAPAccumulator`, which implements it; the protocol is `box_ap`'s).
+    detections: list (one entry per image) of (masks, scores [n], classes [n]); ground_truth: list of (masks, classes [m]); masks is a
+    [n, H, W] uint8 / bool tensor on the device, a host tensor (uploaded) or a list of RLE dicts (decoded on the device).
+    -> dict(AP, AP50, AP75, classes, gt, dets)."""
+    acc = MaskAPAccumulator(iou_thresholds, max_dets)
+    for (dm, ds, dc), (gm, gc) in zip(detections, ground_truth):
+        acc.update(dm, ds, dc, gm, gc)
+    return acc.compute()

@@ -1200,6 +1200,113 @@ def rle_to_string(counts):
     return buf.raw[:rc]
 
 
+def rle_from_string(s):
+    """host: the bytes / str stored under "counts" in COCO json -> run lengths, a host int32 tensor (the int32 view of uint32 that
+    `rle_encode` and `rle_to_string` use); the inverse of `rle_to_string`"""
+    if isinstance(s, str):
+        s = s.encode("ascii")
+    if not isinstance(s, (bytes, bytearray)):
+        raise TypeError(f"ape_amd.ops.rle_from_string: counts string must be bytes or str, got {type(s).__name__}")
+    s = bytes(s)
+    out = torch.empty((max(1, len(s)),), dtype=torch.int32)        # a run takes at least one character
+    rc = _lib.load().ape_hip_rle_from_string(s, len(s), ctypes.c_void_p(out.data_ptr()), out.numel())
+    if rc < 0:
+        raise RuntimeError("ape_hip_rle_from_string: buffer too small")
+    return out[:rc].clone()
+
+
+def rle_decode(counts, nruns, H, W, out=None):
+    """COCO run lengths back to masks: counts [n, cap] int32 (view of uint32) and nruns [n] int32 on the device, as `rle_encode`
+    returns them -> uint8 [n, H, W] holding 0 / 1.  min(nruns[i], cap) runs are read; pixels past their sum are 0, a run that would
+    pass H * W is clipped.  out: optional preallocated contiguous uint8 [n, H, W]."""
+    _dev(counts, nruns, out)
+    if counts.dtype != torch.int32 or nruns.dtype != torch.int32:
+        raise TypeError(f"ape_amd.ops.rle_decode: counts / nruns must be int32, got {counts.dtype} / {nruns.dtype}")
+    if counts.dim() != 2 or not counts.is_contiguous() or not nruns.is_contiguous() or tuple(nruns.shape) != (counts.shape[0],):
+        raise ValueError("ape_amd.ops.rle_decode: counts / nruns must be contiguous [n, cap] / [n]")
+    n, cap = counts.shape
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or (n > 0 and cap < 1):
+        raise ValueError(f"ape_amd.ops.rle_decode: H = {H}, W = {W}, cap = {cap} must all be at least 1")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=counts.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous():
+        raise ValueError(f"ape_amd.ops.rle_decode: out must be contiguous uint8 [{n}, {H}, {W}]")
+    if n == 0:
+        return out
+    lib = _lib.load()
+    words = lib.ape_hip_rle_decode_workspace_words(n, cap)
+    if words < 0:
+        raise ValueError("ape_amd.ops.rle_decode: workspace exceeds 2^31 words; decode fewer masks per call")
+    ws = torch.empty((words,), dtype=torch.int32, device=counts.device)
+    rc = lib.ape_hip_rle_decode(_p(counts), _p(nruns), n, cap, H, W, _p(ws), _p(out), _stream())
+    _lib.check(rc, "ape_hip_rle_decode")
+    return out
+
+
+def _byte_masks(masks, who):
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    if masks.dtype != torch.uint8:
+        raise TypeError(f"ape_amd.ops.{who}: masks are uint8 or bool, got {masks.dtype}")
+    if masks.dim() != 3 or not masks.is_contiguous():
+        raise ValueError(f"ape_amd.ops.{who}: masks must be contiguous [n, H, W], got shape {tuple(masks.shape)} stride {masks.stride()}")
+    return masks
+
+
+def mask_pack_bits(masks):
+    """[n, H, W] uint8 / bool masks (non-zero = foreground, contiguous, any base address) -> (bits int64 [n, words], area int64 [n]):
+    pixel p of the flattened mask is bit p % 64 of word p // 64 (int64 storage of the library's uint64 words), the unused high bits
+    of the last word are zero; area = foreground pixels per mask.  One launch and a memset node, no synchronisation."""
+    _dev(masks)
+    masks = _byte_masks(masks, "mask_pack_bits")
+    n, H, W = masks.shape
+    npix = H * W
+    words = (npix + 63) // 64
+    bits = torch.empty((n, words), dtype=torch.int64, device=masks.device)
+    area = torch.empty((n,), dtype=torch.int64, device=masks.device)
+    rc = _lib.load().ape_hip_mask_pack_bits(_p(masks), n, npix, npix, _p(bits), words, _p(area), _stream())
+    _lib.check(rc, "ape_hip_mask_pack_bits")
+    return bits, area
+
+
+def bitmask_pair_counts(a_bits, b_bits, out=None):
+    """inter[i, j] = number of bits set in both a_bits[i] and b_bits[j] (int64 [n, words] / [m, words] as `mask_pack_bits` returns
+    them) -> int64 [n, m].  out: optional contiguous int64 [n, m], OVERWRITTEN."""
+    _dev(a_bits, b_bits, out)
+    for t, name in ((a_bits, "a_bits"), (b_bits, "b_bits")):
+        if t.dtype != torch.int64:
+            raise TypeError(f"ape_amd.ops.bitmask_pair_counts: {name} is {t.dtype}; packed masks are int64 words")
+        if t.dim() != 2 or not t.is_contiguous():
+            raise ValueError(f"ape_amd.ops.bitmask_pair_counts: {name} must be contiguous [rows, words]")
+    if a_bits.shape[1] != b_bits.shape[1]:
+        raise ValueError(f"ape_amd.ops.bitmask_pair_counts: a_bits has {a_bits.shape[1]} words per mask, b_bits has {b_bits.shape[1]}")
+    n, m, words = a_bits.shape[0], b_bits.shape[0], a_bits.shape[1]
+    if out is None:
+        out = torch.empty((n, m), dtype=torch.int64, device=a_bits.device)
+    if out.dtype != torch.int64 or tuple(out.shape) != (n, m) or not out.is_contiguous():
+        raise ValueError(f"ape_amd.ops.bitmask_pair_counts: out must be contiguous int64 [{n}, {m}]")
+    rc = _lib.load().ape_hip_bitmask_pair_counts(_p(a_bits), n, words, _p(b_bits), m, words, words, _p(out), m, _stream())
+    _lib.check(rc, "ape_hip_bitmask_pair_counts")
+    return out
+
+
+def mask_pair_iou(a, b):
+    """pairwise IoU of two sets of masks on the device: a [n, H, W], b [m, H, W] uint8 / bool -> (iou float64 [n, m], inter int64
+    [n, m], area_a int64 [n], area_b int64 [m]); iou = inter / (area_a + area_b - inter), 0 where the union is empty.  One pack per
+    side and one pair-count launch; the counts are exact."""
+    _dev(a, b)
+    a, b = _byte_masks(a, "mask_pair_iou"), _byte_masks(b, "mask_pair_iou")
+    if tuple(a.shape[1:]) != tuple(b.shape[1:]):
+        raise ValueError(f"ape_amd.ops.mask_pair_iou: masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}")
+    a_bits, area_a = mask_pack_bits(a)
+    b_bits, area_b = mask_pack_bits(b)
+    inter = bitmask_pair_counts(a_bits, b_bits)
+    union = area_a[:, None] + area_b[None, :] - inter
+    iou = torch.where(union > 0, inter.double() / union.clamp_min(1).double(), torch.zeros((), dtype=torch.float64, device=inter.device))
+    return iou, inter, area_a, area_b
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Data-dependent selections (csrc/topk.hip): fixed shapes, no host synchronisation
 # ------------------------------------------------------------------------------------------------------------------

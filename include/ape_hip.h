@@ -575,6 +575,34 @@ int ape_hip_label_hist_lds_bins(void);
 int ape_hip_label_pair_hist(const void* a, int a_bytes, const void* b, int b_bytes, size_t n, int na, int nb, int a_ignore,
                             int b_ignore, int64_t* hist, int64_t* rejected, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance-mask scoring (ape_amd/evaluation.py, mask_ap): mask IoU on bit-packed masks, and the inverse of the RLE wire
+ * format above.  Integer arithmetic throughout: exact for any order of arrival.  -- csrc/maskiou.hip
+ *   mask_pack_bits     : n byte masks of npix pixels (non-zero = foreground; `stride` bytes from one mask to the next; the base
+ *                        may be ANY byte address) -> bits [n, ldb] 64-bit words, pixel p = bit p %% 64 of word p / 64, the unused
+ *                        high bits of the last word zero (words npix / 64 rounded up .. ldb of a row are left alone), and
+ *                        area [n] int64 foreground counts, WRITTEN (zeroed by a memset node of the stream, then counted).
+ *   bitmask_pair_counts: inter[i][j] = sum over w < words of popcount(a[i][w] & b[j][w]), a [n, lda], b [m, ldb] -> int64
+ *                        [n, ldi], SET by the call (when the word axis is split over workgroups the call zeroes inter with a
+ *                        memset node first: a captured graph replays to the same result).  n == 0 or m == 0: a no-op;
+ *                        words == 0 writes zeros.
+ *   rle_decode         : counts [n, cap] uint32 + nruns [n] (column-major runs starting with the zeros, what rle_encode
+ *                        writes) -> masks [n, H, W] uint8 0 / 1 row-major.  Reads min(nruns[i], cap) runs; pixels past the sum
+ *                        of the runs are 0; a run that would pass H * W is clipped; writes exactly the n * H * W bytes.
+ *                        workspace: ape_hip_rle_decode_workspace_words(n, cap) uint32 (negative: too large).
+ *   rle_from_string    : HOST function, the ASCII string of `len` bytes -> counts; returns the number of runs (-needed if cap
+ *                        is too small; counts may be NULL with cap 0 to ask).
+ * Argument errors are reported before any HIP call; no allocation, no host synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_mask_pack_bits(const uint8_t* masks, int n, size_t npix, size_t stride, uint64_t* bits, size_t ldb, int64_t* area,
+                           void* stream);
+int ape_hip_bitmask_pair_counts(const uint64_t* a, int n, size_t lda, const uint64_t* b, int m, size_t ldb, size_t words,
+                                int64_t* inter, size_t ldi, void* stream);
+int ape_hip_rle_decode_workspace_words(int n, int cap);
+int ape_hip_rle_decode(const uint32_t* counts, const uint32_t* nruns, int n, int cap, int H, int W, uint32_t* workspace,
+                       uint8_t* masks, void* stream);
+int ape_hip_rle_from_string(const char* s, int len, uint32_t* counts, int cap);
+
 #ifdef __cplusplus
 }
 #endif
