@@ -171,6 +171,11 @@ SIGNATURES = {
     "ape_hip_rle_decode_workspace_words": (c_int, [c_int, c_int]),
     "ape_hip_rle_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "ape_hip_rle_from_string": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "ape_hip_mask_pack_rows": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "ape_hip_bitmask_boundary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p,
+                                         c_void_p]),
+    "ape_hip_bitmask_boundary_tile": (c_int, [c_int, c_int, c_int, ctypes.c_size_t, POINTER(c_int), POINTER(c_int)]),
+    "ape_hip_bitmask_unpack_rows": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -539,8 +539,12 @@ class MaskAPAccumulator:
             b = _device_masks(gt_masks, a.device)
             if tuple(a.shape[1:]) != tuple(b.shape[1:]):
                 raise ValueError(f"MaskAPAccumulator.update: prediction masks {tuple(a.shape[1:])} vs ground truth {tuple(b.shape[1:])}")
-            iou = ops.mask_pair_iou(a, b)[0].cpu()
+            iou = self._pair_iou(a, b)
         self.records.append((ds, dc, gc, iou))
+
+    def _pair_iou(self, a, b):
+        """the matching IoU of two non-empty mask sets on one device, a [n, H, W] and b [m, H, W] -> float64 [n, m] on the host"""
+        return ops.mask_pair_iou(a, b)[0].cpu()
 
     def reduce(self, group=None):
         """gather every rank's records (torch.distributed.all_gather_object; every rank ends with all of them, in rank order); a
@@ -563,6 +567,50 @@ def mask_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
     [n, H, W] uint8 / bool tensor on the device, a host tensor (uploaded) or a list of RLE dicts (decoded on the device).
     -> dict(AP, AP50, AP75, classes, gt, dets)."""
     acc = MaskAPAccumulator(iou_thresholds, max_dets)
+    for (dm, ds, dc), (gm, gc) in zip(detections, ground_truth):
+        acc.update(dm, ds, dc, gm, gc)
+    return acc.compute()
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Mask boundaries.  Boundary IoU (Cheng et al., CVPR 2021) is the IoU of the two masks' inner boundary bands, d = 2 % of the image
+# diagonal wide; Boundary AP matches on min(mask IoU, boundary IoU).  The bands are made on the device from row-packed bits
+# (`ops.boundary_pair_iou`, csrc/boundary.hip) and contracted by the same popcount kernel as the masks; only the [n, m] matrix travels.
+# ------------------------------------------------------------------------------------------------------------------
+def boundary_iou(a, b, dilation_ratio=0.02, dilation=None, device=None):
+    """Boundary IoU matrix of two mask sets of one size, float64 [n, m] on the device: the IoU of the inner boundary bands, each
+    `dilation` pixels wide (default: `dilation_ratio` of the image diagonal, `ops.boundary_dilation`), 0 where both bands are empty.
+    The published `boundary_iou` package restated (not installable here: unpinned, like `box_ap`).  a, b: [n, H, W] uint8 / bool on
+    the device, host tensors (uploaded) or lists of RLE dicts (decoded on the device)."""
+    a = _device_masks(a, device)
+    if a is None:
+        raise ValueError("boundary_iou: an empty list has no size; build the [0, h, w] tensor yourself")
+    b = _device_masks(b, a.device)
+    if b is None:
+        raise ValueError("boundary_iou: an empty list has no size; build the [0, h, w] tensor yourself")
+    return ops.boundary_pair_iou(a, b, dilation_ratio, dilation)[0]
+
+
+class BoundaryAPAccumulator(MaskAPAccumulator):
+    """COCO-style Boundary AP of a dataset (the second segmentation metric of the LVIS challenge): `MaskAPAccumulator` with the matching
+    IoU min(mask IoU, boundary IoU), both counted on the device in `ops.boundary_pair_iou` -- one row pack and one erosion per side,
+    two popcount contractions.  Inputs, `update` / `reduce` / `compute` and the result keys are `MaskAPAccumulator`'s.
+    Out of scope, like its siblings: crowd regions, area ranges (APs / APm / APl), polygon ground truth, the LVIS federated protocol
+    and boundary PQ.  The `boundary_iou` package is not a dependency of this package: unpinned."""
+
+    def __init__(self, iou_thresholds=None, max_dets=100, device=None, dilation_ratio=0.02):
+        super().__init__(iou_thresholds, max_dets, device)
+        self.dilation_ratio = float(dilation_ratio)
+
+    def _pair_iou(self, a, b):
+        biou, iou = ops.boundary_pair_iou(a, b, self.dilation_ratio)[:2]
+        return torch.minimum(iou, biou).cpu()
+
+
+def boundary_ap(detections, ground_truth, iou_thresholds=None, max_dets=100, dilation_ratio=0.02):
+    """COCO-style Boundary AP (see `BoundaryAPAccumulator`, which implements it): `mask_ap` with min(mask IoU, boundary IoU) as the
+    matching IoU.  detections / ground_truth as for `mask_ap`.  -> dict(AP, AP50, AP75, classes, gt, dets)."""
+    acc = BoundaryAPAccumulator(iou_thresholds, max_dets, dilation_ratio=dilation_ratio)
     for (dm, ds, dc), (gm, gc) in zip(detections, ground_truth):
         acc.update(dm, ds, dc, gm, gc)
     return acc.compute()

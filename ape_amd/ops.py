@@ -1308,6 +1308,134 @@ def mask_pair_iou(a, b):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Mask boundaries (csrc/boundary.hip): Boundary IoU (Cheng et al., CVPR 2021) on row-packed masks
+# ------------------------------------------------------------------------------------------------------------------
+def boundary_dilation(H, W, ratio=0.02):
+    """host: the width in pixels of the boundary band of an H x W image, the published rule: `ratio` of the image diagonal, rounded
+    with Python's round (half to even), at least 1"""
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"ape_amd.ops.boundary_dilation: H = {H}, W = {W} must both be at least 1")
+    return max(1, int(round(float(ratio) * math.sqrt(H * H + W * W))))
+
+
+def _row_words(W):
+    return (int(W) + 63) // 64
+
+
+def _row_bits(bits, H, W, who):
+    """checks of a row-packed operand; returns (n, H, W, wpr)"""
+    if bits.dtype != torch.int64:
+        raise TypeError(f"ape_amd.ops.{who}: bits are {bits.dtype}; packed masks are int64 words")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"ape_amd.ops.{who}: H = {H}, W = {W} must both be at least 1")
+    wpr = _row_words(W)
+    if bits.dim() != 2 or not bits.is_contiguous() or bits.shape[1] != H * wpr:
+        raise ValueError(f"ape_amd.ops.{who}: bits must be contiguous [n, H * wpr = {H * wpr}] for {H} x {W} masks, got shape "
+                         f"{tuple(bits.shape)} stride {bits.stride()}")
+    return bits.shape[0], H, W, wpr
+
+
+def mask_pack_rows(masks):
+    """[n, H, W] uint8 / bool masks (non-zero = foreground, contiguous, any base address) -> (bits int64 [n, H * wpr], area int64 [n]),
+    ROW-PACKED: pixel (y, x) is bit x % 64 of word y * wpr + x // 64 with wpr = ceil(W / 64), the unused high bits of every row's last
+    word are zero -- the layout `bitmask_boundary` erodes, and a valid operand of `bitmask_pair_counts` as it is.  One launch and a
+    memset node, no synchronisation."""
+    _dev(masks)
+    masks = _byte_masks(masks, "mask_pack_rows")
+    n, H, W = masks.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"ape_amd.ops.mask_pack_rows: masks of {H} x {W} pixels")
+    words = H * _row_words(W)
+    bits = torch.empty((n, words), dtype=torch.int64, device=masks.device)
+    area = torch.empty((n,), dtype=torch.int64, device=masks.device)
+    if n == 0:
+        return bits, area
+    rc = _lib.load().ape_hip_mask_pack_rows(_p(masks), n, H, W, _p(bits), words, _p(area), _stream())
+    _lib.check(rc, "ape_hip_mask_pack_rows")
+    return bits, area
+
+
+def bitmask_boundary(bits, H, W, d):
+    """the inner boundary bands of row-packed masks (`mask_pack_rows`): bits int64 [n, H * wpr] -> (bbits int64 [n, H * wpr], barea int64
+    [n]); a band is the mask without its erosion by the (2 d + 1)^2 square, everything outside the image counting as background (the
+    image edge erodes like a mask edge).  d >= 1 pixels (`boundary_dilation`).  One launch and a memset node, no synchronisation."""
+    _dev(bits)
+    n, H, W, wpr = _row_bits(bits, H, W, "bitmask_boundary")
+    d = int(d)
+    if d < 1:
+        raise ValueError(f"ape_amd.ops.bitmask_boundary: d = {d} must be at least 1")
+    bbits = torch.empty_like(bits)
+    barea = torch.empty((n,), dtype=torch.int64, device=bits.device)
+    if n == 0:
+        return bbits, barea
+    rc = _lib.load().ape_hip_bitmask_boundary(_p(bits), n, H, W, d, H * wpr, _p(bbits), H * wpr, _p(barea), _stream())
+    _lib.check(rc, "ape_hip_bitmask_boundary")
+    return bbits, barea
+
+
+def bitmask_unpack_rows(bits, H, W, out=None):
+    """row-packed bits int64 [n, H * wpr] -> uint8 [n, H, W] holding 0 / 1, the inverse of `mask_pack_rows`.
+    out: optional preallocated contiguous uint8 [n, H, W] (any base address); exactly its bytes are written."""
+    _dev(bits, out)
+    n, H, W, wpr = _row_bits(bits, H, W, "bitmask_unpack_rows")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=bits.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous():
+        raise ValueError(f"ape_amd.ops.bitmask_unpack_rows: out must be contiguous uint8 [{n}, {H}, {W}]")
+    if n == 0:
+        return out
+    rc = _lib.load().ape_hip_bitmask_unpack_rows(_p(bits), n, H, W, H * wpr, _p(out), _stream())
+    _lib.check(rc, "ape_hip_bitmask_unpack_rows")
+    return out
+
+
+def _dilation(H, W, dilation_ratio, dilation, who):
+    d = boundary_dilation(H, W, dilation_ratio) if dilation is None else int(dilation)
+    if d < 1:
+        raise ValueError(f"ape_amd.ops.{who}: dilation = {d} must be at least 1")
+    return d
+
+
+def mask_boundary(masks, dilation_ratio=0.02, dilation=None):
+    """[n, H, W] uint8 / bool masks -> uint8 [n, H, W] of 0 / 1, each mask's inner boundary band (the published `mask_to_boundary`):
+    `dilation` pixels wide, by default `dilation_ratio` of the image diagonal (`boundary_dilation`)"""
+    _dev(masks)
+    masks = _byte_masks(masks, "mask_boundary")
+    n, H, W = masks.shape
+    d = _dilation(H, W, dilation_ratio, dilation, "mask_boundary")
+    bits, _ = mask_pack_rows(masks)
+    bbits, _ = bitmask_boundary(bits, H, W, d)
+    return bitmask_unpack_rows(bbits, H, W)
+
+
+def boundary_pair_iou(a, b, dilation_ratio=0.02, dilation=None):
+    """pairwise Boundary IoU and mask IoU of two sets of masks on the device: a [n, H, W], b [m, H, W] uint8 / bool ->
+    (biou float64 [n, m], iou float64 [n, m], binter int64 [n, m], inter int64 [n, m], barea_a [n], barea_b [m], area_a [n], area_b [m]).
+    biou is the IoU of the two boundary bands (`bitmask_boundary`), iou that of the masks; either is 0 where its union is empty.
+    One row pack and one boundary launch per side, then two `bitmask_pair_counts`; the counts are exact."""
+    _dev(a, b)
+    a, b = _byte_masks(a, "boundary_pair_iou"), _byte_masks(b, "boundary_pair_iou")
+    if tuple(a.shape[1:]) != tuple(b.shape[1:]):
+        raise ValueError(f"ape_amd.ops.boundary_pair_iou: masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}")
+    H, W = a.shape[1:]
+    d = _dilation(H, W, dilation_ratio, dilation, "boundary_pair_iou")
+    a_bits, area_a = mask_pack_rows(a)
+    b_bits, area_b = mask_pack_rows(b)
+    a_band, barea_a = bitmask_boundary(a_bits, H, W, d)
+    b_band, barea_b = bitmask_boundary(b_bits, H, W, d)
+    inter = bitmask_pair_counts(a_bits, b_bits)
+    binter = bitmask_pair_counts(a_band, b_band)
+    zero = torch.zeros((), dtype=torch.float64, device=inter.device)
+
+    def ratio(i, sa, sb):
+        union = sa[:, None] + sb[None, :] - i
+        return torch.where(union > 0, i.double() / union.clamp_min(1).double(), zero)
+    return ratio(binter, barea_a, barea_b), ratio(inter, area_a, area_b), binter, inter, barea_a, barea_b, area_a, area_b
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Data-dependent selections (csrc/topk.hip): fixed shapes, no host synchronisation
 # ------------------------------------------------------------------------------------------------------------------
 def _level_arrays(level_shapes):

@@ -603,6 +603,32 @@ int ape_hip_rle_decode(const uint32_t* counts, const uint32_t* nruns, int n, int
                        uint8_t* masks, void* stream);
 int ape_hip_rle_from_string(const char* s, int len, uint32_t* counts, int cap);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mask boundaries (ape_amd/evaluation.py, boundary_ap): the inner boundary band of Boundary IoU (Cheng et al., CVPR 2021) on
+ * ROW-PACKED masks.  Integer arithmetic throughout: exact.  -- csrc/boundary.hip
+ * Row-packed layout of an H x W mask: pixel (y, x) is bit x %% 64 of word y * wpr + x / 64, wpr = W / 64 rounded up; the unused
+ * high bits of each row's last word are zero.  A mask takes H * wpr words; ldb / ldo are the words from one mask to the next.
+ * A row-packed [n, ldb] array is a valid operand of ape_hip_bitmask_pair_counts with words = H * wpr.
+ *   mask_pack_rows     : n byte masks [H, W], contiguous (non-zero = foreground; the base may be ANY byte address; nothing outside
+ *                        the n * H * W bytes is read) -> row-packed bits [n, ldb] and area [n] int64 foreground counts, WRITTEN
+ *                        (zeroed by a memset node of the stream, then counted).
+ *   bitmask_boundary   : bbits = bits & ~eroded, where eroded(y, x) = 1 iff every pixel (y', x') with |y' - y| <= d and
+ *                        |x' - x| <= d lies inside the image and is set (the image edge erodes like a mask edge), and
+ *                        barea [n] = popcount of each band, WRITTEN (memset node, then counted).  Not in place.  d >= 1; with
+ *                        2 d + 1 > H or > W the band is the mask.  One output row needs (2 d + 1) * 16 bytes of LDS (d <= 2047
+ *                        at 64 KiB): a larger d that is not of the trivial kind is an argument error.
+ *   bitmask_boundary_tile: HOST, the tile the boundary kernel uses for (H, W, d) with `lds_limit` bytes of LDS per workgroup
+ *                        (0 = ask the current device): rows and 64-pixel words of output per workgroup; returns the LDS bytes of
+ *                        a workgroup (0 with a 0 x 0 tile when the band is the mask), negative on error.
+ *   bitmask_unpack_rows: row-packed bits -> masks [n, H, W] uint8 of 0 / 1; writes exactly the n * H * W bytes (any base address).
+ * Argument errors are reported before any HIP call; no allocation, no host synchronisation; n == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_mask_pack_rows(const uint8_t* masks, int n, int H, int W, uint64_t* bits, size_t ldb, int64_t* area, void* stream);
+int ape_hip_bitmask_boundary(const uint64_t* bits, int n, int H, int W, int d, size_t ldb, uint64_t* bbits, size_t ldo, int64_t* barea,
+                             void* stream);
+int ape_hip_bitmask_boundary_tile(int H, int W, int d, size_t lds_limit, int* tile_rows, int* tile_words);
+int ape_hip_bitmask_unpack_rows(const uint64_t* bits, int n, int H, int W, size_t ldb, uint8_t* masks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
