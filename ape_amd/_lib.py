@@ -166,6 +166,7 @@ SIGNATURES = {
     "ape_hip_label_pair_hist": (c_int, [c_void_p, c_int, c_void_p, c_int, ctypes.c_size_t, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                         c_void_p]),
     "ape_hip_mask_pack_bits": (c_int, [c_void_p, c_int, ctypes.c_size_t, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
+    "ape_hip_mask_paired_counts": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, ctypes.c_size_t, c_int, ctypes.c_size_t, c_void_p, c_void_p]),
     "ape_hip_bitmask_pair_counts": (c_int, [c_void_p, c_int, ctypes.c_size_t, c_void_p, c_int, ctypes.c_size_t, ctypes.c_size_t, c_void_p,
                                             ctypes.c_size_t, c_void_p]),
     "ape_hip_rle_decode_workspace_words": (c_int, [c_int, c_int]),

@@ -9,6 +9,9 @@
 //                         A base pointer that is not a multiple of 16 keeps the aligned loads: the 16 pixels of a lane then lie in two
 //                         neighbouring vectors, the second of which is the next lane's (one shuffle); only the vectors that overlap
 //                         the mask's first or last bytes are read byte by byte, so nothing outside the mask is touched.
+//   mask_paired_counts  : for n (a_i, b_i) pairs of byte masks the three integers |a_i & b_i|, |a_i|, |b_i| -- what the referring-expression
+//                         scores need -- in ONE pass over the bytes: the pack's loads and marks for both sides (each with its own
+//                         misalignment), popcounts in registers, three atomics per wave; no bits are written.
 //   bitmask_pair_counts : inter[i][j] = sum_w popcount(a[i][w] & b[j][w]), a binary GEMM.  A workgroup stages 64 rows of a and 64 rows of
 //                         b over 32 words in LDS, a thread owns 4 x 4 pairs; the word axis is split over workgroups until the grid
 //                         fills the device, and the partial sums then meet in 64-bit integer atomics on a matrix that the call zeroes
@@ -118,6 +121,122 @@ extern "C" int ape_hip_mask_pack_bits(const uint8_t* masks, int n, size_t npix, 
   APE_LAUNCH(mask_pack_bits_kernel, dim3((unsigned)gx, (unsigned)n), dim3(MP_THREADS), 0, st, masks, (long long)npix, (long long)stride,
              (mi_u64*)bits, (long long)ldb, (mi_u64*)area);
   APE_CHECK_LAUNCH("ape_hip_mask_pack_bits");
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ paired counts
+// the marks of MP_UNROLL * 64 consecutive aligned vectors (b[u] of lane l = vector v0 + 64 u + l) -> pieces in pixel order, for a mask
+// whose byte address is s != 0 past a multiple of 16: piece t = the high 16 - s marks of vector t and the low s marks of vector t + 1, the
+// next lane's; lane 63 takes lane 0 of the next unrolled step, and behind the last step `own`, which it has loaded itself.  Called by
+// whole waves.
+__device__ __forceinline__ void mq_pixel_order(uint32_t (&b)[MP_UNROLL], uint32_t own, int s, int lane) {
+#pragma unroll
+  for (int u = 0; u < MP_UNROLL; ++u) {
+    uint32_t nxt = __shfl_down(b[u], 1, 64);
+    const uint32_t wrap = u + 1 < MP_UNROLL ? __shfl(b[(u + 1) % MP_UNROLL], 0, 64) : own;     // b[u + 1] is still in vector order
+    if (lane == 63) nxt = wrap;
+    b[u] = ((b[u] >> s) | (nxt << (16 - s))) & 0xffffu;
+  }
+}
+
+__device__ __forceinline__ uint32_t mq_marks(const uint4& t) {
+  return mp_nib(t.x) | (mp_nib(t.y) << 4) | (mp_nib(t.z) << 8) | (mp_nib(t.w) << 12);
+}
+
+// grid (x, n): the waves of row y walk the pieces (16 pixels) of pair y, MP_UNROLL * 64 pieces (4096 pixels) per wave and step, and add
+// (|a & b|, |a|, |b|) to out[y][0..2].  a and b are read once, with aligned 16-byte loads whatever their two byte addresses are; nothing
+// is stored in between.
+__global__ __launch_bounds__(MP_THREADS) void mask_paired_counts_kernel(const uint8_t* __restrict__ a, long long stride_a,
+                                                                        const uint8_t* __restrict__ b, long long stride_b, long long npix,
+                                                                        mi_u64* __restrict__ out) {
+  const int mi = blockIdx.y;
+  const uint8_t* __restrict__ ma = a + (size_t)mi * stride_a;
+  const uint8_t* __restrict__ mb = b + (size_t)mi * stride_b;
+  const int sa = (int)((uintptr_t)ma & 15), sb = (int)((uintptr_t)mb & 15);
+  const long long pieces = (npix + 15) / 16;
+  const int lane = threadIdx.x & 63;
+  // wave w of workgroup x is wave w * gridDim.x + x of the row: with fewer steps than waves, every workgroup's first wave has one
+  const long long wave = (long long)(threadIdx.x >> 6) * gridDim.x + blockIdx.x, nwaves = (long long)gridDim.x * (MP_THREADS / 64);
+  uint32_t inter = 0, area_a = 0, area_b = 0;                     // a wave counts fewer than 2^32 pixels: npix is below that
+  // the loop bound is the same for every lane of a wave: the shuffles of mq_pixel_order see whole waves
+  for (long long base = wave * (64 * MP_UNROLL); base < pieces; base += nwaves * (64 * MP_UNROLL)) {
+    uint32_t pa[MP_UNROLL], pb[MP_UNROLL];
+    uint32_t own_a = 0, own_b = 0;                                // the vector behind the step's last one: nobody else has loaded it
+    // wave-uniform: every vector of the step, and the one behind it, lies inside both masks (bytes 16 base - s .. 16 (base + 64 U + 1) - s)
+    const bool inner = (base > 0 || (sa | sb) == 0) && 16 * (base + 64 * MP_UNROLL + 1) <= npix;
+    if (inner) {                                                  // 2 * MP_UNROLL loads in flight, nothing decided per lane but lane 63's extra
+      const uint8_t* __restrict__ qa = ma + 16 * (base + lane) - sa;
+      const uint8_t* __restrict__ qb = mb + 16 * (base + lane) - sb;
+      uint4 va[MP_UNROLL], vb[MP_UNROLL], wa = make_uint4(0, 0, 0, 0), wb = make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (int u = 0; u < MP_UNROLL; ++u) va[u] = *reinterpret_cast<const uint4*>(qa + u * 1024);
+#pragma unroll
+      for (int u = 0; u < MP_UNROLL; ++u) vb[u] = *reinterpret_cast<const uint4*>(qb + u * 1024);
+      if (lane == 63) {
+        if (sa != 0) wa = *reinterpret_cast<const uint4*>(qa + (MP_UNROLL - 1) * 1024 + 16);
+        if (sb != 0) wb = *reinterpret_cast<const uint4*>(qb + (MP_UNROLL - 1) * 1024 + 16);
+      }
+#pragma unroll
+      for (int u = 0; u < MP_UNROLL; ++u) {
+        pa[u] = mq_marks(va[u]);
+        pb[u] = mq_marks(vb[u]);
+      }
+      own_a = mq_marks(wa);
+      own_b = mq_marks(wb);
+    } else {                                                      // a step at either end of the masks: every vector checks its bytes
+#pragma unroll
+      for (int u = 0; u < MP_UNROLL; ++u) pa[u] = mp_vector_bits(ma, base + u * 64 + lane, sa, npix);
+#pragma unroll
+      for (int u = 0; u < MP_UNROLL; ++u) pb[u] = mp_vector_bits(mb, base + u * 64 + lane, sb, npix);
+      if (lane == 63) {
+        if (sa != 0) own_a = mp_vector_bits(ma, base + 64 * MP_UNROLL, sa, npix);
+        if (sb != 0) own_b = mp_vector_bits(mb, base + 64 * MP_UNROLL, sb, npix);
+      }
+    }
+    if (sa != 0) mq_pixel_order(pa, own_a, sa, lane);             // uniform over the workgroup
+    if (sb != 0) mq_pixel_order(pb, own_b, sb, lane);
+#pragma unroll
+    for (int u = 0; u < MP_UNROLL; ++u) {
+      inter += (uint32_t)__popc(pa[u] & pb[u]);
+      area_a += (uint32_t)__popc(pa[u]);
+      area_b += (uint32_t)__popc(pb[u]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    inter += __shfl_xor(inter, o, 64);
+    area_a += __shfl_xor(area_a, o, 64);
+    area_b += __shfl_xor(area_b, o, 64);
+  }
+  const uint32_t mine = lane == 0 ? inter : lane == 1 ? area_a : area_b;     // lanes 0..2 carry one sum each
+  if (lane < 3 && mine != 0u) atomicAdd(&out[(size_t)mi * 3 + lane], (mi_u64)mine);
+}
+
+extern "C" int ape_hip_mask_paired_counts(const uint8_t* a, size_t stride_a, const uint8_t* b, size_t stride_b, int n, size_t npix,
+                                          int64_t* out, void* stream) {
+  APE_CHECK_ARG(n >= 0, "ape_hip_mask_paired_counts: n = %d is negative", n);
+  if (n == 0) return 0;
+  APE_CHECK_ARG(out && (npix == 0 || (a && b)), "ape_hip_mask_paired_counts: null pointer");
+  APE_CHECK_ARG(n <= 65535, "ape_hip_mask_paired_counts: n = %d pairs (at most 65535 per call)", n);
+  APE_CHECK_ARG(npix < ((size_t)1 << 32), "ape_hip_mask_paired_counts: a mask of %zu pixels is too large (below 2^32)", npix);
+  APE_CHECK_ARG((stride_a >= npix && stride_b >= npix) || n == 1,
+                "ape_hip_mask_paired_counts: stride %zu / %zu is less than the %zu pixels of a mask", stride_a, stride_b, npix);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(int64_t), st) != hipSuccess) {
+    ape_set_error("ape_hip_mask_paired_counts: memset failed");
+    return -2;
+  }
+  if (npix == 0) return 0;
+  // a workgroup per wave step while that stays below about 8 workgroups per CU over all pairs (one pair of 1024^2 is 256 steps: every CU
+  // reads a part; the waves of a workgroup that find no step leave at once), then several steps per wave
+  const size_t steps = ((npix + 15) / 16 + 64 * MP_UNROLL - 1) / (64 * MP_UNROLL);
+  size_t gx = steps;
+  const size_t want = ((size_t)8 * ape_cu_count() + n - 1) / n;
+  if (gx > want) gx = want;
+  if (gx < 1) gx = 1;
+  APE_LAUNCH(mask_paired_counts_kernel, dim3((unsigned)gx, (unsigned)n), dim3(MP_THREADS), 0, st, a, (long long)stride_a, b, (long long)stride_b,
+             (long long)npix, (mi_u64*)out);
+  APE_CHECK_LAUNCH("ape_hip_mask_paired_counts");
   return 0;
 }
 

@@ -1270,6 +1270,33 @@ def mask_pack_bits(masks):
     return bits, area
 
 
+def mask_paired_counts(a, b, out=None):
+    """PAIRED counts of two mask sets of one size: a, b [n, H, W] uint8 / bool (non-zero = foreground; contiguous, any base address,
+    the two dtypes may differ) -> int64 [n, 3], row i = (|a_i & b_i|, |a_i|, |b_i|): what a referring-expression score needs of pair
+    i.  One pass over the bytes -- no bits are stored, no n x n matrix is counted (`mask_pair_iou` does both); one launch and a memset
+    node, no synchronisation; the counts are exact.  out: optional contiguous int64 [n, 3], OVERWRITTEN (rows of a larger buffer do).
+    A host tensor raises like everywhere in this module (RuntimeError: there is no CPU path)."""
+    _dev(a, b, out)
+    a, b = _byte_masks(a, "mask_paired_counts"), _byte_masks(b, "mask_paired_counts")
+    if tuple(a.shape[1:]) != tuple(b.shape[1:]):
+        raise ValueError(f"ape_amd.ops.mask_paired_counts: masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"ape_amd.ops.mask_paired_counts: {a.shape[0]} masks against {b.shape[0]}; the counts are of pairs (a_i, b_i)")
+    if a.device != b.device or (out is not None and out.device != a.device):
+        raise ValueError("ape_amd.ops.mask_paired_counts: a, b and out must be on one device")
+    n, H, W = a.shape
+    npix = H * W
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.int64, device=a.device)
+    if out.dtype != torch.int64 or tuple(out.shape) != (n, 3) or not out.is_contiguous():
+        raise ValueError(f"ape_amd.ops.mask_paired_counts: out must be contiguous int64 [{n}, 3]")
+    if n == 0:
+        return out
+    rc = _lib.load().ape_hip_mask_paired_counts(_p(a), npix, _p(b), npix, n, npix, _p(out), _stream())
+    _lib.check(rc, "ape_hip_mask_paired_counts")
+    return out
+
+
 def bitmask_pair_counts(a_bits, b_bits, out=None):
     """inter[i, j] = number of bits set in both a_bits[i] and b_bits[j] (int64 [n, words] / [m, words] as `mask_pack_bits` returns
     them) -> int64 [n, m].  out: optional contiguous int64 [n, m], OVERWRITTEN."""

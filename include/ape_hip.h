@@ -582,6 +582,11 @@ int ape_hip_label_pair_hist(const void* a, int a_bytes, const void* b, int b_byt
  *                        may be ANY byte address) -> bits [n, ldb] 64-bit words, pixel p = bit p %% 64 of word p / 64, the unused
  *                        high bits of the last word zero (words npix / 64 rounded up .. ldb of a row are left alone), and
  *                        area [n] int64 foreground counts, WRITTEN (zeroed by a memset node of the stream, then counted).
+ *   mask_paired_counts : n PAIRS of byte masks (a_i at a + i * stride_a, b_i at b + i * stride_b, npix bytes each, non-zero =
+ *                        foreground, ANY byte addresses, the two sides' alignments independent) -> out [n][3] int64 =
+ *                        (|a_i & b_i|, |a_i|, |b_i|), WRITTEN (zeroed by a memset node of the stream, then counted): one pass
+ *                        over the bytes, nothing outside them is read, no workspace.  n == 0: a no-op; npix == 0 writes zeros.
+ *                        n <= 65535, npix < 2^32, stride >= npix unless n == 1.
  *   bitmask_pair_counts: inter[i][j] = sum over w < words of popcount(a[i][w] & b[j][w]), a [n, lda], b [m, ldb] -> int64
  *                        [n, ldi], SET by the call (when the word axis is split over workgroups the call zeroes inter with a
  *                        memset node first: a captured graph replays to the same result).  n == 0 or m == 0: a no-op;
@@ -596,6 +601,8 @@ int ape_hip_label_pair_hist(const void* a, int a_bytes, const void* b, int b_byt
  * ------------------------------------------------------------------------------------------- */
 int ape_hip_mask_pack_bits(const uint8_t* masks, int n, size_t npix, size_t stride, uint64_t* bits, size_t ldb, int64_t* area,
                            void* stream);
+int ape_hip_mask_paired_counts(const uint8_t* a, size_t stride_a, const uint8_t* b, size_t stride_b, int n, size_t npix, int64_t* out,
+                               void* stream);
 int ape_hip_bitmask_pair_counts(const uint64_t* a, int n, size_t lda, const uint64_t* b, int m, size_t ldb, size_t words,
                                 int64_t* inter, size_t ldi, void* stream);
 int ape_hip_rle_decode_workspace_words(int n, int cap);
