@@ -177,6 +177,8 @@ SIGNATURES = {
                                          c_void_p]),
     "ape_hip_bitmask_boundary_tile": (c_int, [c_int, c_int, c_int, ctypes.c_size_t, POINTER(c_int), POINTER(c_int)]),
     "ape_hip_bitmask_unpack_rows": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p]),
+    "ape_hip_box_cover_overlaps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_void_p]),
 }
 
 _lib = None

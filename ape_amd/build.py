@@ -22,14 +22,24 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # attention: the softmax never produces a NaN (key 0 is visible to every query, masked scores are -inf and only ever meet finite
 # maxima), so fmaxf needs no NaN-quieting: under the default IEEE mode hipcc canonicalises every operand of a max with a
 # `v_max x, x` -- 30 of the ~160 VALU instructions a wave issues per key tile in a VALU-bound kernel
-FILE_FLAGS = {"ffn_fused.hip": ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form=0"],
+# boxcover: the IoU is held to bit equality with host float32 arithmetic -- a multiply and an add stay two roundings
+FILE_FLAGS = {"boxcover.hip": FLAGS + ["-ffp-contract=off"],
+              "ffn_fused.hip": ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form=0"],
               "attention.hip": FLAGS + ["-fno-honor-nans", "-mno-amdgpu-ieee"]}
 
 
+# objects that go to the END of the link line, behind the alphabetical rest.  The link order fixes the order in which the code objects
+# register with the HIP runtime and where the host code of each file lies.  Measured on an MI355X with boxcover.hip.o in its
+# alphabetical place (third): the benchmark's detections of the last step differ from run to run (scores by up to 4e-4, hence other
+# top-k queries; 5 runs of 5, each unlike the others), although no benchmark kernel or host function differs; with the object last the dumped outputs are
+# identical to those of the library without it (6 runs of 6, array for array).  The cause of that sensitivity lies outside boxcover.hip, whose kernel
+# the benchmark never launches, and has not been found; until it is, a new file must not move the existing objects.
+LINK_LAST = ("boxcover.hip",)
+
+
 def _sources():
-    return sorted(
-        os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip") or f.endswith(".cpp")
-    )
+    names = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") or f.endswith(".cpp"))
+    return [os.path.join(CSRC, f) for f in names if f not in LINK_LAST] + [os.path.join(CSRC, f) for f in LINK_LAST if f in names]
 
 
 def _digest():
@@ -42,6 +52,7 @@ def _digest():
             h.update(fh.read())
     h.update(" ".join(FLAGS).encode())
     h.update(repr(sorted(FILE_FLAGS.items())).encode())
+    h.update(repr(LINK_LAST).encode())
     return h.hexdigest()
 
 

@@ -1463,6 +1463,97 @@ def boundary_pair_iou(a, b, dilation_ratio=0.02, dilation=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Box-proposal coverage (csrc/boxcover.hip): the greedy assignment behind AR@100 / AR@1000 by area
+# ------------------------------------------------------------------------------------------------------------------
+# the reference's area ranges (lvis_evaluation.py:311-315): all, small, medium, large -- both ends inclusive
+BOX_COVER_RANGES = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))
+BOX_COVER_LIMITS = (100, 1000)
+_BOX_COVER_COMBOS = {}
+
+
+def box_cover_combinations(device, ranges=None, limits=None):
+    """(ranges float32 [C, 2], limits int32 [C]) on `device`: the full product of `limits` (outer; default 100, 1000; <= 0 = no limit)
+    and `ranges` (inner, (lo, hi) pairs; default the reference's all / small / medium / large), C = 8 by default in the order
+    AR@100, ARs@100, ARm@100, ARl@100, AR@1000, ...  Built once per device and pair of lists, then reused."""
+    ranges = BOX_COVER_RANGES if ranges is None else tuple((float(lo), float(hi)) for lo, hi in ranges)
+    limits = BOX_COVER_LIMITS if limits is None else tuple(int(v) for v in limits)
+    key = (torch.device(device), ranges, limits)
+    if key not in _BOX_COVER_COMBOS:
+        r = torch.tensor([list(p) for _ in limits for p in ranges], dtype=torch.float32).reshape(-1, 2)
+        k = torch.tensor([v for v in limits for _ in ranges], dtype=torch.int32)
+        _BOX_COVER_COMBOS[key] = (r.to(device), k.to(device))
+    return _BOX_COVER_COMBOS[key]
+
+
+def _boxes_f32(t, name):
+    if not torch.is_tensor(t) or t.dtype != torch.float32:
+        raise TypeError(f"ape_amd.ops.box_cover_overlaps: {name} must be a float32 tensor, got {t.dtype if torch.is_tensor(t) else type(t)}")
+    if t.dim() != 2 or t.shape[1] != 4 or not t.is_contiguous():
+        raise ValueError(f"ape_amd.ops.box_cover_overlaps: {name} must be contiguous [k, 4] XYXY, got shape {tuple(t.shape)} "
+                         f"stride {t.stride()}")
+    return t
+
+
+def box_cover_overlaps(proposals, gt_boxes, gt_areas=None, ranges=None, limits=None, out=None, match=None):
+    """The greedy coverage of ground-truth boxes by proposals that box-proposal recall is made of (the loop of the reference's
+    `_evaluate_box_proposals`), for C (area range, proposal limit) combinations in one launch.
+    proposals float32 [n, 4] XYXY in DESCENDING SCORE ORDER, gt_boxes float32 [m, 4] XYXY, gt_areas float32 [m] (default: the box area
+    (x2 - x1) * (y2 - y1); COCO / LVIS annotations carry their own `area`, the segment's), ranges float32 [C, 2] = (lo, hi) with
+    limits int32 [C] (<= 0: no limit) -- two tensors of one length, taken as they are; or lists / None for both, expanded by
+    `box_cover_combinations` (default C = 8: limits 100, 1000 outer, the reference's four area ranges inner).
+    -> (overlaps float32 [C, m], match int32 [C, m]).  For combination c over the first min(n, limit_c) proposals and the ground truth
+    whose area lies in [lo_c, hi_c] (inclusive), min(rows, columns) times: every unused column's best is its maximum IoU over the unused
+    rows (ties: the lowest row), the best column is the maximum of those (ties: the lowest column) -- torch.max(dim=0)'s first-index
+    rule; overlaps[c, g] = that IoU, match[c, g] = the proposal's row, and both are used up.  In-range ground truth never reached
+    gets (0, -1), ground truth out of range (-1, -1).  IoU is float32, inter / ((area_p + area_g) - inter) or 0 without intersection,
+    bit for bit what the same operations give on the host.  The n x m matrix is never stored; m <= 4096, n <= 65535.
+    out / match: optional contiguous [C, m] float32 / int32, OVERWRITTEN entirely.  One launch, no synchronisation.  A host tensor
+    raises RuntimeError (there is no CPU path)."""
+    who = "ape_amd.ops.box_cover_overlaps"
+    proposals, gt_boxes = _boxes_f32(proposals, "proposals"), _boxes_f32(gt_boxes, "gt_boxes")
+    n, m = proposals.shape[0], gt_boxes.shape[0]
+    if gt_areas is not None:
+        if not torch.is_tensor(gt_areas) or gt_areas.dtype != torch.float32:
+            raise TypeError(f"{who}: gt_areas must be a float32 tensor")
+        if tuple(gt_areas.shape) != (m,) or not gt_areas.is_contiguous():
+            raise ValueError(f"{who}: gt_areas must be contiguous [{m}], got shape {tuple(gt_areas.shape)} stride {gt_areas.stride()}")
+    given = torch.is_tensor(ranges), torch.is_tensor(limits)
+    if given[0] != given[1]:
+        raise ValueError(f"{who}: ranges and limits are two tensors of one length, or lists / None for both")
+    if given[0]:
+        if ranges.dtype != torch.float32 or limits.dtype != torch.int32:
+            raise TypeError(f"{who}: ranges are float32 and limits int32, got {ranges.dtype} and {limits.dtype}")
+        if ranges.dim() != 2 or ranges.shape[1] != 2 or tuple(limits.shape) != (ranges.shape[0],) or not ranges.is_contiguous() \
+                or not limits.is_contiguous():
+            raise ValueError(f"{who}: ranges must be contiguous [C, 2] and limits [C], got {tuple(ranges.shape)} and {tuple(limits.shape)}")
+    _dev(proposals, gt_boxes, gt_areas, out, match, *((ranges, limits) if given[0] else ()))
+    dev = proposals.device
+    if not given[0]:
+        ranges, limits = box_cover_combinations(dev, ranges, limits)
+    if any(t is not None and t.device != dev for t in (gt_boxes, gt_areas, ranges, limits, out, match)):
+        raise ValueError(f"{who}: all tensors must be on one device")
+    if m > 4096 or n > 65535:
+        raise ValueError(f"{who}: {n} proposals against {m} ground-truth boxes (at most 65535 against 4096 per call)")
+    C = ranges.shape[0]
+    if out is None:
+        out = torch.empty((C, m), dtype=torch.float32, device=dev)
+    if match is None:
+        match = torch.empty((C, m), dtype=torch.int32, device=dev)
+    if out.dtype != torch.float32 or tuple(out.shape) != (C, m) or not out.is_contiguous():
+        raise ValueError(f"{who}: out must be contiguous float32 [{C}, {m}]")
+    if match.dtype != torch.int32 or tuple(match.shape) != (C, m) or not match.is_contiguous():
+        raise ValueError(f"{who}: match must be contiguous int32 [{C}, {m}]")
+    if m == 0 or C == 0:
+        return out, match
+    if gt_areas is None:
+        gt_areas = (gt_boxes[:, 2] - gt_boxes[:, 0]) * (gt_boxes[:, 3] - gt_boxes[:, 1])
+    rc = _lib.load().ape_hip_box_cover_overlaps(_p(proposals), n, _p(gt_boxes), _p(gt_areas), m, _p(ranges), _p(limits), C, _p(out),
+                                                _p(match), _stream())
+    _lib.check(rc, "ape_hip_box_cover_overlaps")
+    return out, match
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # Data-dependent selections (csrc/topk.hip): fixed shapes, no host synchronisation
 # ------------------------------------------------------------------------------------------------------------------
 def _level_arrays(level_shapes):

@@ -636,6 +636,27 @@ int ape_hip_bitmask_boundary(const uint64_t* bits, int n, int H, int W, int d, s
 int ape_hip_bitmask_boundary_tile(int H, int W, int d, size_t lds_limit, int* tile_rows, int* tile_words);
 int ape_hip_bitmask_unpack_rows(const uint64_t* bits, int n, int H, int W, size_t ldb, uint8_t* masks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Box proposals (ape_amd/evaluation.py, proposal_recall): the greedy one-to-one coverage behind AR@100 / AR@1000 by area, for C
+ * (area range, proposal limit) combinations of one image in ONE launch.  float32 with a fixed order of operations and no
+ * multiply-add contraction: the result equals host float32 arithmetic bit for bit.  -- csrc/boxcover.hip
+ *   box_cover_overlaps : proposals [n, 4] XYXY in DESCENDING SCORE ORDER, gt [m, 4] XYXY, gt_area [m], ranges [C, 2] = (lo, hi),
+ *                        limits [C] int32 (<= 0: no limit), all float32 on the device, 4-byte aligned -> overlaps [C, m] float32
+ *                        and match [C, m] int32, EVERY element WRITTEN.  For combination c: GT g is in range iff
+ *                        lo_c <= gt_area[g] <= hi_c; the rows are the first n_c = min(n, limit_c) proposals;
+ *                        iou = inter > 0 ? inter / ((area_p + area_g) - inter) : 0 with area = (x2 - x1) * (y2 - y1) (no clamp),
+ *                        inter = max(min(px2, gx2) - max(px1, gx1), 0) * max(min(py2, gy2) - max(py1, gy1), 0).  Then
+ *                        min(n_c, GT in range) times: each unused in-range column's best is its maximum IoU over the unused
+ *                        rows (ties: the LOWEST row), the best column is the maximum of those (ties: the LOWEST column);
+ *                        overlaps[c][g] = that IoU, match[c][g] = the row, and row and column are used up.  In-range GT never
+ *                        reached (n_c is smaller than their number; n == 0) get (0, -1), GT out of range get (-1, -1).
+ *                        The n x m matrix is never stored: no workspace.  m <= 4096, n <= 65535, C <= 65535;
+ *                        m == 0 or C == 0: a no-op.
+ * Argument errors are reported before any HIP call; no allocation, no host synchronisation; capturable.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_box_cover_overlaps(const float* proposals, int n, const float* gt, const float* gt_area, int m, const float* ranges,
+                               const int* limits, int C, float* overlaps, int* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
