@@ -179,6 +179,8 @@ SIGNATURES = {
     "ape_hip_bitmask_unpack_rows": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.c_size_t, c_void_p, c_void_p]),
     "ape_hip_box_cover_overlaps": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                            c_void_p]),
+    "ape_hip_coco_match": (c_int, [c_void_p, c_int, c_int, ctypes.c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1551,6 +1552,114 @@ def box_cover_overlaps(proposals, gt_boxes, gt_areas=None, ranges=None, limits=N
                                                 _p(match), _stream())
     _lib.check(rc, "ape_hip_box_cover_overlaps")
     return out, match
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# COCO matching (csrc/boxcover.hip, coco_match_kernel): COCOeval.evaluateImg for all classes, area ranges and thresholds of an image
+# ------------------------------------------------------------------------------------------------------------------
+# pycocotools' Params: iouThrs = numpy.linspace(.5, .95, 10) -- NOT 0.5 + 0.05 * i, which differs from it in the last bit at 0.85 and
+# 0.90 --, areaRng all / small / medium / large with both ends inside, recThrs = numpy.linspace(0, 1, 101)
+COCO_THRESHOLDS = tuple(float(v) for v in np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True))
+COCO_RANGES = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))
+COCO_MAX_GT = 4096
+COCO_MAX_DET = 65535
+_COCO_TABLES = {}
+
+
+def coco_match_tables(device, thresholds=None, ranges=None):
+    """(thresholds float64 [T], ranges float64 [A, 2]) on `device` from lists (default: COCO's ten thresholds and four area ranges).
+    Built once per device and pair of lists, then reused."""
+    thresholds = COCO_THRESHOLDS if thresholds is None else tuple(float(v) for v in thresholds)
+    ranges = COCO_RANGES if ranges is None else tuple((float(lo), float(hi)) for lo, hi in ranges)
+    key = (torch.device(device), thresholds, ranges)
+    if key not in _COCO_TABLES:
+        t = torch.tensor(list(thresholds), dtype=torch.float64)
+        r = torch.tensor([list(p) for p in ranges], dtype=torch.float64).reshape(-1, 2)
+        _COCO_TABLES[key] = (t.to(device), r.to(device))
+    return _COCO_TABLES[key]
+
+
+def coco_match(iou, det_order, det_offsets, gt_order, gt_offsets, gt_crowd, gt_area, det_area, thresholds=None, ranges=None,
+               match=None, flag=None):
+    """COCOeval's matching of ONE image's detections to its ground truth (`evaluateImg`), for all K class groups x A area ranges x T
+    IoU thresholds in one launch.
+    iou float64 [n, m] (unit inner stride, any row stride): detections x ground truth of all classes, a crowd column already holding
+    inter / area_det; det_order int32 [n']: rows of iou grouped by class, in DESCENDING SCORE order inside a group and already cut to the
+    largest maxDets, det_offsets int32 [K + 1] the group boundaries (det_offsets[0] = 0, det_offsets[K] = n'); gt_order int32 [m']:
+    columns grouped by class in annotation order, gt_offsets int32 [K + 1]; gt_crowd uint8 [m], gt_area float64 [m] and det_area
+    float64 [n] by original column / row; thresholds float64 [T] and ranges float64 [A, 2] = (lo, hi) as tensors, or lists / None
+    (`coco_match_tables`; default numpy.linspace(.5, .95, 10) and all / small / medium / large).
+    -> (match int32 [A, T, n'], flag uint8 [A, T, n']) by position in det_order: the matched original column or -1, and 1 = true
+    positive, 0 = false positive, 2 = ignored.  For (group, (lo, hi), t): a ground truth is ignored iff crowd or area < lo or
+    area > hi; the detections go in group order, lim = min(t, 1 - 1e-10); phase 1 takes among the not-ignored ground truth not yet
+    taken with iou >= lim the maximum IoU, the LAST in group order among equals; only if there is none, phase 2 chooses the same way among
+    the ignored.  A crowd is never used up, anything else once.  flag = 2 if the match is ignored, else 1; without a match 2 if
+    det_area lies outside [lo, hi], else 0.
+    A group holds at most 4096 ground truths and 65535 detections; the group sizes live on the device, so the check is made on what the
+    shapes give without reading them: m' <= 4096 and n' <= 65535 (ValueError).  match / flag: optional contiguous buffers, OVERWRITTEN
+    entirely (no memset, no atomics: a captured graph replays to the same bytes).  One launch, no synchronisation.  A host tensor raises
+    RuntimeError (there is no CPU path)."""
+    who = "ape_amd.ops.coco_match"
+    given = torch.is_tensor(thresholds), torch.is_tensor(ranges)
+    named = [("iou", iou, torch.float64, 2), ("det_order", det_order, torch.int32, 1), ("det_offsets", det_offsets, torch.int32, 1),
+             ("gt_order", gt_order, torch.int32, 1), ("gt_offsets", gt_offsets, torch.int32, 1), ("gt_crowd", gt_crowd, torch.uint8, 1),
+             ("gt_area", gt_area, torch.float64, 1), ("det_area", det_area, torch.float64, 1)]
+    if given[0]:
+        named.append(("thresholds", thresholds, torch.float64, 1))
+    if given[1]:
+        named.append(("ranges", ranges, torch.float64, 2))
+    for name, t, dtype, dim in named:
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise TypeError(f"{who}: {name} must be a {dtype} tensor, got {t.dtype if torch.is_tensor(t) else type(t)}")
+        if t.dim() != dim:
+            raise ValueError(f"{who}: {name} must have {dim} dimension(s), got shape {tuple(t.shape)}")
+        if name != "iou" and not t.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous, got stride {t.stride()}")
+    n, m = iou.shape
+    if m > 1 and iou.stride(1) != 1:
+        raise ValueError(f"{who}: iou must have unit inner stride, got stride {iou.stride()}")
+    ld = m if n <= 1 else iou.stride(0)
+    if ld < m:
+        raise ValueError(f"{who}: iou rows overlap (stride {iou.stride()} for {m} columns)")
+    nd, ng, K = det_order.shape[0], gt_order.shape[0], det_offsets.shape[0] - 1
+    if K < 0 or gt_offsets.shape[0] != K + 1:
+        raise ValueError(f"{who}: det_offsets and gt_offsets must both be [K + 1], got {tuple(det_offsets.shape)} and {tuple(gt_offsets.shape)}")
+    if K == 0 and nd > 0:
+        raise ValueError(f"{who}: {nd} detections in no group (K = 0)")
+    if tuple(gt_crowd.shape) != (m,) or tuple(gt_area.shape) != (m,) or tuple(det_area.shape) != (n,):
+        raise ValueError(f"{who}: gt_crowd and gt_area must be [{m}] and det_area [{n}], got {tuple(gt_crowd.shape)}, "
+                         f"{tuple(gt_area.shape)} and {tuple(det_area.shape)}")
+    if given[1] and ranges.shape[1] != 2:
+        raise ValueError(f"{who}: ranges must be [A, 2], got {tuple(ranges.shape)}")
+    if ng > COCO_MAX_GT or nd > COCO_MAX_DET:
+        raise ValueError(f"{who}: {nd} grouped detections against {ng} grouped ground truths (at most {COCO_MAX_DET} against "
+                         f"{COCO_MAX_GT} per group and call)")
+    _dev(*(t for _, t, _, _ in named), match, flag)
+    dev = iou.device
+    if not all(given):
+        dt, dr = coco_match_tables(dev, None if given[0] else thresholds, None if given[1] else ranges)
+        thresholds, ranges = thresholds if given[0] else dt, ranges if given[1] else dr
+    if any(t is not None and t.device != dev for t in (det_order, det_offsets, gt_order, gt_offsets, gt_crowd, gt_area, det_area, thresholds,
+                                                       ranges, match, flag)):
+        raise ValueError(f"{who}: all tensors must be on one device")
+    T, A = thresholds.shape[0], ranges.shape[0]
+    if K * A * T >= 2 ** 31:
+        raise ValueError(f"{who}: K x A x T = {K * A * T} problems (fewer than 2^31 per call)")
+    if match is None:
+        match = torch.empty((A, T, nd), dtype=torch.int32, device=dev)
+    if flag is None:
+        flag = torch.empty((A, T, nd), dtype=torch.uint8, device=dev)
+    if match.dtype != torch.int32 or tuple(match.shape) != (A, T, nd) or not match.is_contiguous():
+        raise ValueError(f"{who}: match must be contiguous int32 [{A}, {T}, {nd}]")
+    if flag.dtype != torch.uint8 or tuple(flag.shape) != (A, T, nd) or not flag.is_contiguous():
+        raise ValueError(f"{who}: flag must be contiguous uint8 [{A}, {T}, {nd}]")
+    if nd == 0 or A == 0 or T == 0:
+        return match, flag
+    rc = _lib.load().ape_hip_coco_match(_p(iou), n, m, ld, _p(det_order), nd, _p(det_offsets), _p(gt_order), ng, _p(gt_offsets), K,
+                                        _p(gt_crowd), _p(gt_area), _p(det_area), _p(thresholds), T, _p(ranges), A, _p(match), _p(flag),
+                                        _stream())
+    _lib.check(rc, "ape_hip_coco_match")
+    return match, flag
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -657,6 +657,30 @@ int ape_hip_bitmask_unpack_rows(const uint64_t* bits, int n, int H, int W, size_
 int ape_hip_box_cover_overlaps(const float* proposals, int n, const float* gt, const float* gt_area, int m, const float* ranges,
                                const int* limits, int C, float* overlaps, int* match, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO matching (ape_amd/evaluation.py, COCOAccumulator): pycocotools' COCOeval.evaluateImg -- the greedy, ignore-aware assignment of an
+ * image's detections to its ground truth -- for all K class groups x A area ranges x T IoU thresholds in ONE launch, one wave per
+ * (group, range, threshold).  Only float64 comparisons: the result equals the host's.  -- csrc/boxcover.hip
+ *   coco_match : iou [n, m] float64 with row stride ld (elements; a crowd column holds inter / area_det); det_order [nd] int32 = rows
+ *                of iou grouped by class, DESCENDING SCORE inside a group, det_offsets [K + 1] int32 with det_offsets[0] = 0 and
+ *                det_offsets[K] = nd; gt_order [ng] int32 = columns grouped by class in annotation order, gt_offsets [K + 1];
+ *                gt_crowd [m] uint8, gt_area [m] float64, det_area [n] float64 by ORIGINAL column / row; thresholds [T] float64;
+ *                ranges [A, 2] float64 = (lo, hi) -> match [A, T, nd] int32 (the original column, or -1) and flag [A, T, nd] uint8
+ *                (1 true positive, 0 false positive, 2 ignored) by position in det_order, every element of a group WRITTEN.
+ *                For (group, (lo, hi), t): ground truth g is ignored iff crowd[g] or area[g] < lo or area[g] > hi.  Detections in
+ *                group order, lim = min(t, 1 - 1e-10): phase 1 takes, among not-ignored ground truth not yet taken with
+ *                iou >= lim, the maximum IoU (ties: the LAST in group order); only without one, phase 2 chooses the same way among
+ *                the ignored.  A crowd is never used up, anything else once.  flag = 2 if the match is ignored, else 1; without
+ *                a match 2 if det_area lies outside [lo, hi], else 0.
+ *                nd <= 65535 and ng <= 4096 (a group holds no more), K * A * T < 2^31; nd == 0, A == 0 or T == 0: a no-op.
+ *                Offsets and orders are data: values outside their arrays are clamped or skipped, never used as an index.
+ * Argument errors are reported before any HIP call; no allocation, no memset, no atomics, no host synchronisation; capturable.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_coco_match(const double* iou, int n, int m, size_t ld, const int* det_order, int nd, const int* det_offsets,
+                       const int* gt_order, int ng, const int* gt_offsets, int K, const uint8_t* gt_crowd, const double* gt_area,
+                       const double* det_area, const double* thresholds, int T, const double* ranges, int A, int* match,
+                       uint8_t* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
