@@ -1319,6 +1319,14 @@ def bitmask_pair_counts(a_bits, b_bits, out=None):
     return out
 
 
+def count_iou(inter, area_a, area_b, crowd=None):
+    """integer counts inter [n, m], area_a [n], area_b [m] -> float64 [n, m]: inter / union, in a crowd column (crowd bool [m], COCO's
+    rule) inter / area_a, 0 where the denominator is 0.  Pure torch, on any device."""
+    union = area_a[:, None] + area_b[None, :] - inter
+    den = union if crowd is None else torch.where(crowd[None, :], area_a[:, None].expand_as(union), union)
+    return torch.where(den > 0, inter.double() / den.clamp_min(1).double(), torch.zeros((), dtype=torch.float64, device=inter.device))
+
+
 def mask_pair_iou(a, b):
     """pairwise IoU of two sets of masks on the device: a [n, H, W], b [m, H, W] uint8 / bool -> (iou float64 [n, m], inter int64
     [n, m], area_a int64 [n], area_b int64 [m]); iou = inter / (area_a + area_b - inter), 0 where the union is empty.  One pack per
@@ -1327,12 +1335,9 @@ def mask_pair_iou(a, b):
     a, b = _byte_masks(a, "mask_pair_iou"), _byte_masks(b, "mask_pair_iou")
     if tuple(a.shape[1:]) != tuple(b.shape[1:]):
         raise ValueError(f"ape_amd.ops.mask_pair_iou: masks of {tuple(a.shape[1:])} against masks of {tuple(b.shape[1:])}")
-    a_bits, area_a = mask_pack_bits(a)
-    b_bits, area_b = mask_pack_bits(b)
+    (a_bits, area_a), (b_bits, area_b) = mask_pack_bits(a), mask_pack_bits(b)
     inter = bitmask_pair_counts(a_bits, b_bits)
-    union = area_a[:, None] + area_b[None, :] - inter
-    iou = torch.where(union > 0, inter.double() / union.clamp_min(1).double(), torch.zeros((), dtype=torch.float64, device=inter.device))
-    return iou, inter, area_a, area_b
+    return count_iou(inter, area_a, area_b), inter, area_a, area_b
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1455,12 +1460,7 @@ def boundary_pair_iou(a, b, dilation_ratio=0.02, dilation=None):
     b_band, barea_b = bitmask_boundary(b_bits, H, W, d)
     inter = bitmask_pair_counts(a_bits, b_bits)
     binter = bitmask_pair_counts(a_band, b_band)
-    zero = torch.zeros((), dtype=torch.float64, device=inter.device)
-
-    def ratio(i, sa, sb):
-        union = sa[:, None] + sb[None, :] - i
-        return torch.where(union > 0, i.double() / union.clamp_min(1).double(), zero)
-    return ratio(binter, barea_a, barea_b), ratio(inter, area_a, area_b), binter, inter, barea_a, barea_b, area_a, area_b
+    return count_iou(binter, barea_a, barea_b), count_iou(inter, area_a, area_b), binter, inter, barea_a, barea_b, area_a, area_b
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -1560,7 +1560,7 @@ def box_cover_overlaps(proposals, gt_boxes, gt_areas=None, ranges=None, limits=N
 # pycocotools' Params: iouThrs = numpy.linspace(.5, .95, 10) -- NOT 0.5 + 0.05 * i, which differs from it in the last bit at 0.85 and
 # 0.90 --, areaRng all / small / medium / large with both ends inside, recThrs = numpy.linspace(0, 1, 101)
 COCO_THRESHOLDS = tuple(float(v) for v in np.linspace(0.5, 0.95, int(np.round((0.95 - 0.5) / 0.05)) + 1, endpoint=True))
-COCO_RANGES = ((0.0, 1e5 ** 2), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e5 ** 2))
+COCO_RANGES = BOX_COVER_RANGES                            # one tuple: COCOeval's areaRng is the proposal scorer's
 COCO_MAX_GT = 4096
 COCO_MAX_DET = 65535
 _COCO_TABLES = {}

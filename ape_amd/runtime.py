@@ -157,7 +157,7 @@ class GraphedForward:
         self.max_out_pixels = max_out_pixels          # any_size: largest output frame (height * width) a slot can hold
         # "bitmask": pred_masks [n, H, W] bool on the host (the reference's output contract, ~1 MB per mask over PCIe);
         # "rle": the evaluators' wire format instead -- the pasted masks are run-length encoded on the device
-        # (ops.rle_encode) and only the runs travel; instances carry `pred_masks_rle` (ape_amd/evaluation.py);
+        # (ops.rle_encode) and only the runs travel; instances carry `pred_masks_rle` (ape_amd/evaluation/wire.py);
         # "both": the bitmasks reach this rank's host exactly as with "bitmask" AND the run lengths are produced next to them
         # (`ticket.runs`, what dp.DataParallelRunner(gather_masks=True) all-gathers across ranks): a data-parallel rank then does
         # everything a single-GPU run does, plus the exchange
