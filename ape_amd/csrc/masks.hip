@@ -128,6 +128,13 @@ extern "C" int ape_hip_roi_align_bits(const uint8_t* bits, int H, int W, const f
   return 0;
 }
 
+// Source coordinate of a paste tap, clamped to [-2, P] before it is floored and converted.  A degenerate box (x1 == x0 or y1 == y0; the
+// callers paste all k rows and drop the empty boxes afterwards) makes it +-inf or NaN: the conversion saturated to INT_MAX, the `+ 1` of
+// the upper tap overflowed, and hipcc -- free to assume that signed addition does not wrap -- tested `lower > -2` in place of
+// `upper >= 0`, which let the wrapped index through at(): a read 2 GiB behind the mask.  Every tap outside [0, P) reads zero, so for a
+// finite coordinate the clamp changes no output; NaN becomes -2 (fmaxf returns its other operand): a degenerate row is all zeros.
+__device__ __forceinline__ float paste_coord(float f, int P) { return fminf(fmaxf(f, -2.f), (float)P); }
+
 // one thread = 16 consecutive output pixels of one row
 __global__ __launch_bounds__(256) void paste_bits_kernel(const uint8_t* __restrict__ m, int P, const float* __restrict__ boxes, int n,
                                                          int Ho, int Wo, uint8_t* __restrict__ out) {
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(256) void paste_bits_kernel(const uint8_t* __restri
   const float x0 = boxes[q * 4 + 0], y0 = boxes[q * 4 + 1], x1 = boxes[q * 4 + 2], y1 = boxes[q * 4 + 3];
   const float gy = ((float)y + 0.5f - y0) / (y1 - y0) * 2.f - 1.f;
   // grid_sample, align_corners=False: ix = ((g + 1) * size - 1) / 2 ; zeros padding
-  const float fy = ((gy + 1.f) * (float)P - 1.f) * 0.5f;
+  const float fy = paste_coord(((gy + 1.f) * (float)P - 1.f) * 0.5f, P);
   const float fly = floorf(fy);
   const int iy0 = (int)fly, iy1 = iy0 + 1;
   const float ly = fy - fly;
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(256) void paste_bits_kernel(const uint8_t* __restri
   for (int i = 0; i < 16; ++i) {
     const int x = xb + i;
     const float gx = ((float)x + 0.5f - x0) / (x1 - x0) * 2.f - 1.f;
-    const float fx = ((gx + 1.f) * (float)P - 1.f) * 0.5f;
+    const float fx = paste_coord(((gx + 1.f) * (float)P - 1.f) * 0.5f, P);
     const float flx = floorf(fx);
     const int ix0 = (int)flx, ix1 = ix0 + 1;
     const float lx = fx - flx;
