@@ -280,7 +280,7 @@ __global__ __launch_bounds__(TK_THREADS) void topk_stage1_kernel(const float* __
   for (int j = 0; j < PER; ++j) {
     const int e = j * TK_THREADS + threadIdx.x;
     const float v = e < n ? x[start + e] : 0.f;
-    kk[j] = e < n ? ordkey(sig ? sigmoid_f(v) : v) : 0u;
+    kk[j] = e < n ? ordkey(sig ? sigmoid_f(v) : v + 0.f) : 0u;      // + 0.f: -0.0 -> +0.0, the two zeros are ONE key (tie rule: lowest index)
   }
   block_topk_regs<PER>(kk, n, jobs.seg_k[seg], (uint32_t)start, comp, hist, sh, wcnt);
   ws[(size_t)job * 1024 + threadIdx.x] = comp[threadIdx.x];
@@ -365,7 +365,7 @@ __global__ __launch_bounds__(TK_THREADS) void proposal_order_kernel(const int32_
   u64* work = po_lds;
   u64* srt = po_lds + npad;
   for (int p = threadIdx.x; p < npad; p += TK_THREADS)     // padding: distinct values below every real composite (low word >= 2^32 - 8192)
-    work[p] = p < n ? (((u64)ordkey(logit[cand[p]]) << 32) | (u64)(0xffffffffu - (uint32_t)p)) : (u64)(npad - 1 - p);
+    work[p] = p < n ? (((u64)ordkey(logit[cand[p]] + 0.f) << 32) | (u64)(0xffffffffu - (uint32_t)p)) : (u64)(npad - 1 - p);   // + 0.f: -0.0 == +0.0
   __syncthreads();
   for (int k = 2; k <= 1024; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {

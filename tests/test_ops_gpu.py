@@ -1211,6 +1211,9 @@ def test_enc_finalize(ops):
     ([(32, 32), (16, 16), (8, 8), (4, 4), (2, 2)], 1000, 300, "ties"),
     ([(16, 16), (8, 8), (4, 4), (2, 2), (1, 1)], 1000, 100, "random"),
     ([(40, 27), (20, 14), (10, 7)], 300, 90, "random"),
+    ([(320, 308), (160, 154), (80, 77), (40, 39), (20, 20)], 1000, 900, "random"),      # 32 elements per thread in the level and fallback segments
+    ([(8, 8), (4, 4), (2, 2), (1, 1)], 1000, 900, "random"),                            # more queries than tokens
+    ([(256, 256), (128, 128), (64, 64), (32, 32), (16, 16)], 1000, 901, "random"),      # a quota that does not divide
 ])
 def test_select_proposals(ops, shapes, k, nq, mode):
     T = sum(h * w for h, w in shapes)
@@ -1229,11 +1232,22 @@ def test_select_proposals(ops, shapes, k, nq, mode):
 
 # (900, 1203, 500): LVIS vocabulary with top-500 -> the 64-elements-per-thread stage-1 instantiation; (900, 1203, 900): (lists x k)
 # beyond stage 2's LDS -> the intermediate merge level (no configuration raises from inside model.forward)
-@pytest.mark.parametrize("Q,K,topk", [(900, 80, 100), (900, 400, 300), (900, 1, 1), (300, 7, 500), (1024, 3, 100), (900, 1203, 500),
-                                      (900, 1203, 900)])
-def test_detections(ops, Q, K, topk):
+_DET_SHAPES = [(900, 80, 100), (900, 400, 300), (900, 1, 1), (300, 7, 500), (1024, 3, 100), (900, 1203, 500), (900, 1203, 900)]
+
+
+# score_thresh 0.05: a strict comparison inside class_sort; padded: the logits are a view of a [Q, K + 3] buffer whose slack is NaN
+@pytest.mark.parametrize("Q,K,topk,score_thresh,padded",
+                         [pytest.param(Q, K, t, 0.0, False, id=f"{Q}-{K}-{t}") for Q, K, t in _DET_SHAPES]
+                         + [pytest.param(Q, K, t, 0.05, False, id=f"{Q}-{K}-{t}-thresh0.05") for Q, K, t in _DET_SHAPES]
+                         + [pytest.param(900, 80, 100, 0.0, True, id="900-80-100-padded"),
+                            pytest.param(900, 80, 100, 0.05, True, id="900-80-100-thresh0.05-padded")])
+def test_detections(ops, Q, K, topk, score_thresh, padded):
     g = torch.Generator(device="cpu").manual_seed(5)
     logits = (torch.randint(-600, 200, (Q, K), generator=g).float() / 64).to(DEV)
+    if padded:
+        buf = torch.full((Q, K + 3), float("nan"), device=DEV)
+        buf[:, :K] = logits
+        logits = buf[:, :K]
     if K > 2:
         logits[:, 1] = float("-inf")                         # a class switched off (evaluation-dataset mode)
     if Q > 10:
@@ -1244,8 +1258,8 @@ def test_detections(ops, Q, K, topk):
     if Q > 10:
         boxes[7, 2] = float("inf")
     scale = torch.tensor([1024.0, 683.0, 1024.0, 683.0], device=DEV)
-    got = ops.detections(logits, boxes, scale, 0.0, 0.7, topk)
-    ref = ref_ops.detections(logits, boxes, scale, 0.0, 0.7, topk)
+    got = ops.detections(logits, boxes, scale, score_thresh, 0.7, topk)
+    ref = ref_ops.detections(logits, boxes, scale, score_thresh, 0.7, topk)
     k = min(topk, Q * K)
     assert got["det_scores"].shape == (k,)
     assert torch.equal(got["det_query"].cpu(), ref["det_query"].cpu())
