@@ -181,6 +181,9 @@ SIGNATURES = {
                                            c_void_p]),
     "ape_hip_coco_match": (c_int, [c_void_p, c_int, c_int, ctypes.c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "ape_hip_poly_workspace_words": (c_int, [c_int, c_int, c_int, c_int]),
+    "ape_hip_poly_rasterize": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
 }
 
 _lib = None

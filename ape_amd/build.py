@@ -23,6 +23,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # maxima), so fmaxf needs no NaN-quieting: under the default IEEE mode hipcc canonicalises every operand of a max with a
 # `v_max x, x` -- 30 of the ~160 VALU instructions a wave issues per key tile in a VALU-bound kernel
 # boxcover: the IoU is held to bit equality with host float32 arithmetic -- a multiply and an add stay two roundings
+# (polygon.hip, compiled inside boxcover.hip -- PART_OF below -- needs the same: rleFrPoly's `ys + s * t + .5` in double decides boundary
+# pixels, the product and the sum stay two roundings, as in the C code)
 FILE_FLAGS = {"boxcover.hip": FLAGS + ["-ffp-contract=off"],
               "ffn_fused.hip": ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-mllvm", "-amdgpu-mfma-vgpr-form=0"],
               "attention.hip": FLAGS + ["-fno-honor-nans", "-mno-amdgpu-ieee"]}
@@ -35,10 +37,14 @@ FILE_FLAGS = {"boxcover.hip": FLAGS + ["-ffp-contract=off"],
 # identical to those of the library without it (6 runs of 6, array for array).  The cause of that sensitivity lies outside boxcover.hip, whose kernel
 # the benchmark never launches, and has not been found; until it is, a new file must not move the existing objects.
 LINK_LAST = ("boxcover.hip",)
+# files of csrc/ that are NO objects of their own: each is included at the end of the file named here and compiled as part of its object,
+# with that file's flags.  So the link line -- which objects, in which order -- stays what it was (see LINK_LAST: until the cause of that
+# sensitivity is found, new kernels join the last object instead of adding one); for the digests below such a file counts as a header.
+PART_OF = {"polygon.hip": "boxcover.hip"}
 
 
 def _sources():
-    names = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip") or f.endswith(".cpp"))
+    names = sorted(f for f in os.listdir(CSRC) if (f.endswith(".hip") or f.endswith(".cpp")) and f not in PART_OF)
     return [os.path.join(CSRC, f) for f in names if f not in LINK_LAST] + [os.path.join(CSRC, f) for f in LINK_LAST if f in names]
 
 
@@ -46,7 +52,7 @@ def _digest():
     h = hashlib.sha256()
     # EVERY header of csrc/ (round 5: gemm_epi.h was missing here -- an edit of the shared epilogue did not rebuild the library, and one GPU
     # run validated a stale .so)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") or f in PART_OF)
     for f in _sources() + headers + [os.path.join(HERE, "..", "include", "ape_hip.h")]:
         with open(f, "rb") as fh:
             h.update(fh.read())
@@ -69,7 +75,7 @@ def build(force=False, verbose=True):
     # per-object stamps: an object is rebuilt only when its own source, a header of csrc/ (or include/ape_hip.h) or its flags changed --
     # iterating on one kernel then costs one hipcc run, not eighteen
     hh = hashlib.sha256()
-    for f in sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(HERE, "..", "include", "ape_hip.h")]:
+    for f in sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") or f in PART_OF) + [os.path.join(HERE, "..", "include", "ape_hip.h")]:
         with open(f, "rb") as fh:
             hh.update(fh.read())
     headers_digest = hh.hexdigest()

@@ -417,3 +417,8 @@ extern "C" int ape_hip_coco_match(const double* iou, int n, int m, size_t ld, co
   APE_CHECK_LAUNCH("ape_hip_coco_match");
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------------ polygon ground truth
+// polygon.hip (COCO polygons -> masks, ape_hip_poly_rasterize) is compiled as part of this object: same flags (no multiply-add
+// contraction), and the link line keeps the objects it had (ape_amd/build.py, PART_OF)
+#include "polygon.hip"

@@ -1,6 +1,7 @@
 """Scoring a model's output, with the counting on the device (`ape_amd.ops`) and the protocol arithmetic on the host.  Everything is
 imported from here; the modules:
-  wire          the evaluators' wire format: `instances_to_coco_json`, `encode_masks` / `decode_masks` (COCO RLE, run lengths made on the device)
+  wire          the evaluators' wire format: `instances_to_coco_json`, `encode_masks` / `decode_masks` (COCO RLE, run lengths made on the device),
+                and the annotations' side of it: `segmentations_to_masks` / `pack_polygons` (COCO polygons rasterised on the device as annToRLE does)
   ap            COCO-style AP, area range "all", no crowd: `box_ap` (the benchmark's score), `mask_ap`, `boundary_ap` and their accumulators
   coco          COCOeval's full protocol -- crowd, area ranges, AP / AR: `COCOAccumulator`, `coco_eval`, `coco_metrics`
   segmentation  `SemSegAccumulator` (mIoU, fwIoU, mACC, pACC) and `PanopticAccumulator` (PQ, SQ, RQ) on the label-pair histogram
@@ -17,6 +18,7 @@ from .proposals import (ProposalRecallAccumulator, proposal_recall, proposal_rec
                         proposal_recall_thresholds)
 from .referring import ReferringAccumulator, referring_metrics, referring_scores                        # noqa: F401
 from .segmentation import PanopticAccumulator, SemSegAccumulator, panoptic_quality, semantic_metrics    # noqa: F401
-from .wire import decode_masks, encode_masks, instances_to_coco_json, rles_from_runs                    # noqa: F401
+from .wire import (decode_masks, encode_masks, instances_to_coco_json, pack_polygons, rles_from_runs,    # noqa: F401
+                   segmentations_to_masks)
 
 _coco_count_iou = ops.count_iou                           # its name before it moved to ops; tests import it from here

@@ -83,11 +83,38 @@ def _label_map(t, device):
     return t.contiguous().reshape(-1)
 
 
-def _device_masks(masks, device=None):
-    """[n, H, W] masks on the device from a device tensor, a host tensor (uploaded) or a list of RLE dicts (decoded); None for an
-    empty list, which has no size"""
+def _has_polygons(masks):
+    """a list of COCO `segmentation` entries of which at least one is in polygon form (a list of flat coordinate lists)"""
+    return isinstance(masks, (list, tuple)) and any(isinstance(s, (list, tuple)) for s in masks)
+
+
+def mask_size(image_size, *sources):
+    """(H, W) of an image's masks: `image_size` if given, else the size of the first tensor among `sources` ([.., H, W]), else the `size`
+    of the first RLE dict in or among them, else None.  Shapes and host dicts only: never a synchronisation."""
+    if image_size is not None:
+        if len(image_size) != 2:
+            raise ValueError(f"image_size is (H, W), got {image_size!r}")
+        return int(image_size[0]), int(image_size[1])
+    for s in sources:
+        if torch.is_tensor(s) and s.dim() >= 2:
+            return int(s.shape[-2]), int(s.shape[-1])
+    for s in sources:
+        for r in ([s] if isinstance(s, dict) else s if isinstance(s, (list, tuple)) else ()):
+            if isinstance(r, dict) and "size" in r:
+                return int(r["size"][0]), int(r["size"][1])
+    return None
+
+
+def _device_masks(masks, device=None, size=None):
+    """[n, H, W] masks on the device from a device tensor, a host tensor (uploaded), a list of RLE dicts (decoded) or a list of COCO
+    `segmentation` entries holding polygons (rasterised at `size` = (H, W), `segmentations_to_masks`); None for an empty list, which
+    has no size"""
     if isinstance(masks, (list, tuple)):
-        from .wire import decode_masks                    # here, not at the top: wire imports this module
+        from .wire import decode_masks, segmentations_to_masks    # here, not at the top: wire imports this module
+        if _has_polygons(masks):
+            if size is None:
+                raise ValueError("polygon ground truth has no size of its own: pass image_size=(H, W)")
+            return segmentations_to_masks(masks, size[0], size[1], device)
         return decode_masks(masks, device) if len(masks) > 0 else None
     if masks.dim() != 3:
         raise ValueError(f"masks must be [n, H, W], got {tuple(masks.shape)}")

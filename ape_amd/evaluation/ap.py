@@ -3,7 +3,8 @@ image -- boxes (`box_ap`, the benchmark's score), masks (`MaskAPAccumulator`) an
 import torch
 
 from .. import ops
-from ._common import _coco_box_iou, _device_masks, _distributed, _is_instances, gather_objects, instance_fields, run_pairs
+from ._common import (_coco_box_iou, _device_masks, _distributed, _is_instances, gather_objects, instance_fields, mask_size,
+                      run_pairs)
 
 
 def _iou_matrix(a, b):
@@ -107,8 +108,8 @@ class MaskAPAccumulator:
     """COCO-style mask AP of a dataset: the protocol `box_ap` documents, with mask IoU in place of box IoU.  `update` packs each side
     of an image once, counts the whole n x m intersection matrix in one launch (`ops.mask_pair_iou`) and keeps only the image's small
     host record -- scores, classes and the IoU matrix; the per-class greedy matching stays on the host, in `compute`.
-    Out of scope, as for `box_ap`: crowd regions, area ranges (APs / APm / APl), polygon ground truth (there is no rasteriser here)
-    and the LVIS federated protocol.  pycocotools is not a dependency of this package: unpinned."""
+    Ground-truth masks may be COCO polygons (rasterised on the device as pycocotools' annToRLE does: `update`'s `image_size`).
+    Out of scope, as for `box_ap`: crowd regions, area ranges (APs / APm / APl) and the LVIS federated protocol.  pycocotools is not a dependency of this package: unpinned."""
 
     def __init__(self, iou_thresholds=None, max_dets=100, device=None):
         self.iou_thresholds = None if iou_thresholds is None else [float(t) for t in iou_thresholds]
@@ -116,10 +117,12 @@ class MaskAPAccumulator:
         self.device = None if device is None else torch.device(device)
         self.records = []
 
-    def update(self, pred, scores=None, classes=None, gt_masks=None, gt_classes=None):
+    def update(self, pred, scores=None, classes=None, gt_masks=None, gt_classes=None, image_size=None):
         """pred: masks [n, H, W] (uint8 / bool; device tensor, host tensor or list of RLE dicts) with `scores` [n] and `classes` [n],
         or an `Instances` carrying `pred_masks` or `pred_masks_rle` next to `scores` and `pred_classes`;
-        gt_masks: [m, H, W] in any of the three forms, gt_classes [m]"""
+        gt_masks: [m, H, W] in any of the three forms, or a list of COCO `segmentation` entries with polygon lists among them, which
+        are rasterised at image_size = (H, W) -- by default the prediction masks' size, else the size of an RLE dict among the inputs;
+        gt_classes [m]"""
         if _is_instances(pred):
             pred, inst_scores, inst_classes = instance_fields(pred, "masks", "MaskAPAccumulator.update")
             scores = inst_scores if scores is None else scores
@@ -137,7 +140,7 @@ class MaskAPAccumulator:
             iou = torch.zeros((n, m), dtype=torch.float64)
         else:
             a = _device_masks(pred, self.device)
-            b = _device_masks(gt_masks, a.device)
+            b = _device_masks(gt_masks, a.device, mask_size(image_size, a, pred, gt_masks))
             if tuple(a.shape[1:]) != tuple(b.shape[1:]):
                 raise ValueError(f"MaskAPAccumulator.update: prediction masks {tuple(a.shape[1:])} vs ground truth {tuple(b.shape[1:])}")
             iou = self._pair_iou(a, b)
@@ -171,15 +174,17 @@ def mask_ap(detections, ground_truth, iou_thresholds=None, max_dets=100):
 # diagonal wide; Boundary AP matches on min(mask IoU, boundary IoU).  The bands are made on the device from row-packed bits
 # (`ops.boundary_pair_iou`, csrc/boundary.hip) and contracted by the same popcount kernel as the masks; only the [n, m] matrix travels.
 # ------------------------------------------------------------------------------------------------------------------
-def boundary_iou(a, b, dilation_ratio=0.02, dilation=None, device=None):
+def boundary_iou(a, b, dilation_ratio=0.02, dilation=None, device=None, image_size=None):
     """Boundary IoU matrix of two mask sets of one size, float64 [n, m] on the device: the IoU of the inner boundary bands, each
     `dilation` pixels wide (default: `dilation_ratio` of the image diagonal, `ops.boundary_dilation`), 0 where both bands are empty.
     The published `boundary_iou` package restated (not installable here: unpinned, like `box_ap`).  a, b: [n, H, W] uint8 / bool on
-    the device, host tensors (uploaded) or lists of RLE dicts (decoded on the device)."""
-    a = _device_masks(a, device)
+    the device, host tensors (uploaded), lists of RLE dicts (decoded on the device) or lists of COCO `segmentation` entries with
+    polygon lists among them (rasterised at image_size = (H, W); default: the size of a tensor or an RLE dict among the inputs)."""
+    size = mask_size(image_size, a, b)
+    a = _device_masks(a, device, size)
     if a is None:
         raise ValueError("boundary_iou: an empty list has no size; build the [0, h, w] tensor yourself")
-    b = _device_masks(b, a.device)
+    b = _device_masks(b, a.device, size)
     if b is None:
         raise ValueError("boundary_iou: an empty list has no size; build the [0, h, w] tensor yourself")
     return ops.boundary_pair_iou(a, b, dilation_ratio, dilation)[0]
@@ -189,8 +194,7 @@ class BoundaryAPAccumulator(MaskAPAccumulator):
     """COCO-style Boundary AP of a dataset (the second segmentation metric of the LVIS challenge): `MaskAPAccumulator` with the matching
     IoU min(mask IoU, boundary IoU), both counted on the device in `ops.boundary_pair_iou` -- one row pack and one erosion per side,
     two popcount contractions.  Inputs, `update` / `reduce` / `compute` and the result keys are `MaskAPAccumulator`'s.
-    Out of scope, like its siblings: crowd regions, area ranges (APs / APm / APl), polygon ground truth, the LVIS federated protocol
-    and boundary PQ.  The `boundary_iou` package is not a dependency of this package: unpinned."""
+    Out of scope, like its siblings: crowd regions, area ranges (APs / APm / APl), the LVIS federated protocol and boundary PQ.  The `boundary_iou` package is not a dependency of this package: unpinned."""
 
     def __init__(self, iou_thresholds=None, max_dets=100, device=None, dilation_ratio=0.02):
         super().__init__(iou_thresholds, max_dets, device)

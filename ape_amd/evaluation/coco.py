@@ -9,7 +9,7 @@ import torch
 
 from .. import ops
 from ._common import (_AREAS, _coco_box_iou, _device_masks, _distributed, _is_instances, gather_objects, instance_fields,
-                      optional_tail, pick_device)
+                      mask_size, optional_tail, pick_device)
 
 
 def coco_recall_points():
@@ -161,7 +161,8 @@ class COCOAccumulator:
     gt_areas: COCO scores with the annotation's `area`; the default is the box area ("bbox") or the mask area ("segm").  The area of a
     detection is its box w * h or its mask area.  Classes are 0 .. num_classes - 1; one outside raises ValueError, at the latest in
     `compute`.  At most 4096 ground truths and 65535 detections per image.
-    Out of scope: polygon ground truth (rasterise it first), the LVIS federated rules, OpenImages, keypoints."""
+    Ground-truth masks may be COCO polygons (`segmentation` lists, rasterised on the device as pycocotools' annToRLE does: `update`'s
+    `image_size`).  Out of scope: the LVIS federated rules, OpenImages, keypoints."""
 
     def __init__(self, iou_type, num_classes, max_dets=(1, 10, 100), device=None, class_names=None):
         if iou_type not in ("bbox", "segm"):
@@ -178,11 +179,13 @@ class COCOAccumulator:
         self.records = []                                     # host: what `coco_metrics` takes
         self._pending = []                                    # device: enqueued, not read back yet
 
-    def update(self, pred, scores=None, classes=None, gt=None, gt_classes=None, gt_crowd=None, gt_areas=None):
+    def update(self, pred, scores=None, classes=None, gt=None, gt_classes=None, gt_crowd=None, gt_areas=None, image_size=None):
         """One image.  pred: boxes [n, 4] XYXY ("bbox") or masks [n, H, W] as a device tensor, a host tensor or a list of RLE dicts
         ("segm"), with `scores` [n] and `classes` [n]; or an `Instances` carrying `pred_boxes` / `pred_masks` / `pred_masks_rle` next to
         `scores` and `pred_classes`.  gt: boxes [m, 4] (a tensor or a `Boxes`) or masks in any of the three forms, gt_classes [m],
-        gt_crowd [m] (non-zero = a crowd region; default none), gt_areas [m] (see the class).  Host inputs are uploaded."""
+        gt_crowd [m] (non-zero = a crowd region; default none), gt_areas [m] (see the class).  Host inputs are uploaded.
+        "segm" ground truth may also be a list of COCO `segmentation` entries, polygon lists among them: they are rasterised at
+        image_size = (H, W), by default the prediction masks' size, else the size of an RLE dict among the inputs."""
         who = "COCOAccumulator.update"
         segm = self.iou_type == "segm"
         if _is_instances(pred):
@@ -220,7 +223,7 @@ class COCOAccumulator:
             iou, det_area, gt_area = _coco_box_iou(pred.to(dev, torch.float64), gt.to(dev, torch.float64), crowd)
         else:
             a = _device_masks(pred, dev) if n > 0 else None
-            b = _device_masks(gt, dev) if m > 0 else None
+            b = _device_masks(gt, dev, mask_size(image_size, pred, gt)) if m > 0 else None
             if a is not None and b is not None and tuple(a.shape[1:]) != tuple(b.shape[1:]):
                 raise ValueError(f"{who}: prediction masks {tuple(a.shape[1:])} vs ground truth {tuple(b.shape[1:])}")
             a_bits, area_a = ops.mask_pack_bits(a) if n > 0 else (None, torch.zeros(0, dtype=torch.int64, device=dev))

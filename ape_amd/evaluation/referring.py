@@ -4,7 +4,8 @@ which `ops.mask_paired_counts` (csrc/maskiou.hip) counts in one pass over the tw
 import torch
 
 from .. import ops
-from ._common import _device_masks, _distributed, _is_instances, gather_objects, instance_fields, optional_tail, pick_device
+from ._common import (_device_masks, _distributed, _is_instances, gather_objects, instance_fields, mask_size, optional_tail,
+                      pick_device)
 
 _REFER_THRESHOLDS = (5, 6, 7, 8, 9)                       # tenths: P@0.5 .. P@0.9
 
@@ -61,8 +62,9 @@ class ReferringAccumulator:
     int64 [capacity, 3] with a float64 [capacity, 8] companion for the boxes: `update` has `ops.mask_paired_counts` write the sample's
     row directly (`out=` a one-row view) and, when the masks are on the device already, issues no device-to-host copy and no
     synchronisation; the tables grow by doubling with a device-to-device copy, and `compute` reads them back once.
-    Out of scope: the COCO-style AP the reference also prints for these datasets (that is `box_ap` / `mask_ap`), gRefCOCO's N-acc / T-acc,
-    polygon ground truth."""
+    The ground truth may be the annotation's COCO polygons (rasterised on the device as the reference's annToRLE does: `update`'s
+    `image_size`).  Out of scope: the COCO-style AP the reference also prints for these datasets (that is `box_ap` / `mask_ap`), gRefCOCO's
+    N-acc / T-acc."""
 
     def __init__(self, device=None, capacity=256):
         self.device = None if device is None else torch.device(device)
@@ -87,23 +89,25 @@ class ReferringAccumulator:
         return self.n
 
     @staticmethod
-    def _one_mask(mask, device, who):
-        """[1, H, W] on the device from a [H, W] / [1, H, W] tensor (device or host) or one RLE dict"""
-        if isinstance(mask, dict):
-            return _device_masks([mask], device)
+    def _one_mask(mask, device, who, size=None):
+        """[1, H, W] on the device from a [H, W] / [1, H, W] tensor (device or host), one RLE dict or one object's polygon list (rasterised
+        at `size`)"""
+        if isinstance(mask, (dict, list, tuple)):
+            return _device_masks([mask], device, size)
         if mask.dim() == 2:
             mask = mask[None]
         if mask.dim() != 3 or mask.shape[0] != 1:
             raise ValueError(f"ReferringAccumulator.update: {who} must be one mask, [H, W] or [1, H, W], got {tuple(mask.shape)}")
         return _device_masks(mask, device)
 
-    def update(self, pred=None, gt_mask=None, gt_box=None, pred_mask=None, pred_box=None):
+    def update(self, pred=None, gt_mask=None, gt_box=None, pred_mask=None, pred_box=None, image_size=None):
         """One sample.  The prediction is either `pred`, an `Instances` as expression mode returns it (`pred_masks` or `pred_masks_rle`,
         `pred_boxes`, `scores`; the highest-scoring instance is taken, on a tie the first, as the reference's stable sort does), or
         `pred_mask` ([H, W] / [1, H, W] uint8 / bool on the device or the host, or one RLE dict) with an optional `pred_box` (XYXY).
         Neither, or an `Instances` of length 0, is a sample without prediction: it scores as an empty mask, (0, 0, area_gt), and is a
-        box miss.  gt_mask: a device tensor, a host tensor or one RLE dict; gt_box: optional XYXY -- with it the sample takes part in
-        P@k, and then every sample of the dataset must."""
+        box miss.  gt_mask: a device tensor, a host tensor, one RLE dict or the annotation's polygon list (ONE object: a list of flat
+        [x0, y0, x1, y1, ...] lists), which is rasterised at image_size = (H, W) -- by default the predicted mask's size; gt_box:
+        optional XYXY -- with it the sample takes part in P@k, and then every sample of the dataset must."""
         if gt_mask is None:
             raise ValueError("ReferringAccumulator.update: gt_mask is needed")
         if pred is not None and pred_mask is not None:
@@ -129,7 +133,7 @@ class ReferringAccumulator:
             pred_mask = masks[first] if masks is not None else rles[first.start]
             pred_box = pb[first] if with_boxes else None
         dev = pick_device(self.device, gt_mask, pred_mask)
-        gt = self._one_mask(gt_mask, dev, "gt_mask").to(dev)
+        gt = self._one_mask(gt_mask, dev, "gt_mask", mask_size(image_size, pred_mask, gt_mask)).to(dev)
         if pred_mask is None:
             pm = torch.zeros_like(gt)                             # no prediction: the empty mask, (0, 0, area_gt)
         else:

@@ -1245,6 +1245,45 @@ def rle_decode(counts, nruns, H, W, out=None):
     return out
 
 
+def poly_rasterize(xy, vert_offsets, poly_offsets, H, W, out=None):
+    """COCO polygons to masks on the device, pixel for pixel pycocotools' annToRLE (maskApi.c rleFrPoly per polygon, the union per
+    object; csrc/polygon.hip): xy float64 [V, 2] (x, y), vert_offsets int32 [P + 1] (the vertex range of each polygon), poly_offsets
+    int32 [n + 1] (the polygon range of each object), all contiguous and on the device, as `evaluation.pack_polygons` builds them on
+    the host -> (masks uint8 [n, H, W] holding 0 / 1, area int64 [n]).  An object without polygons is an empty mask.  Nothing is read
+    back: offsets and coordinates are data to the kernels (ranges are clamped to their arrays, coordinates to +-65536).
+    out: optional preallocated contiguous uint8 [n, H, W], at any byte address."""
+    _dev(xy, vert_offsets, poly_offsets, out)
+    if xy.dtype != torch.float64:
+        raise TypeError(f"ape_amd.ops.poly_rasterize: xy must be float64, got {xy.dtype}")
+    if vert_offsets.dtype != torch.int32 or poly_offsets.dtype != torch.int32:
+        raise TypeError(f"ape_amd.ops.poly_rasterize: vert_offsets / poly_offsets must be int32, got {vert_offsets.dtype} / {poly_offsets.dtype}")
+    if xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+        raise ValueError(f"ape_amd.ops.poly_rasterize: xy must be contiguous [V, 2], got shape {tuple(xy.shape)} stride {xy.stride()}")
+    if (vert_offsets.dim() != 1 or poly_offsets.dim() != 1 or vert_offsets.numel() < 1 or poly_offsets.numel() < 1
+            or not vert_offsets.is_contiguous() or not poly_offsets.is_contiguous()):
+        raise ValueError("ape_amd.ops.poly_rasterize: vert_offsets / poly_offsets must be contiguous [P + 1] / [n + 1]")
+    V, P, n = xy.shape[0], vert_offsets.numel() - 1, poly_offsets.numel() - 1
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError(f"ape_amd.ops.poly_rasterize: H = {H}, W = {W} must both be at least 1")
+    if out is None:
+        out = torch.empty((n, H, W), dtype=torch.uint8, device=xy.device)
+    _dev(out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous():
+        raise ValueError(f"ape_amd.ops.poly_rasterize: out must be contiguous uint8 [{n}, {H}, {W}]")
+    area = torch.empty((n,), dtype=torch.int64, device=xy.device)
+    if n == 0:
+        return out, area
+    lib = _lib.load()
+    words = lib.ape_hip_poly_workspace_words(n, P, H, W)
+    if words < 0:
+        raise ValueError("ape_amd.ops.poly_rasterize: workspace exceeds 2^31 words (or H * W 2^31 pixels); rasterise fewer objects per call")
+    ws = torch.empty((words,), dtype=torch.int64, device=xy.device)
+    rc = lib.ape_hip_poly_rasterize(_p(xy), V, _p(vert_offsets), P, _p(poly_offsets), n, H, W, _p(ws), _p(out), _p(area), _stream())
+    _lib.check(rc, "ape_hip_poly_rasterize")
+    return out, area
+
+
 def _byte_masks(masks, who):
     if masks.dtype == torch.bool:
         masks = masks.view(torch.uint8)

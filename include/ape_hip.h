@@ -681,6 +681,29 @@ int ape_hip_coco_match(const double* iou, int n, int m, size_t ld, const int* de
                        const double* det_area, const double* thresholds, int T, const double* ranges, int A, int* match,
                        uint8_t* flag, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Polygon ground truth (ape_amd/evaluation/wire.py, segmentations_to_masks): COCO `segmentation` polygons -> masks, what the reference
+ * obtains from pycocotools' annToRLE (ape/evaluation/refcocoeval.py:127-131: frPyObjects = cocoapi maskApi.c rleFrPoly per polygon,
+ * then merge = the union), pixel for pixel.  IEEE double with one rounding per operation, integer atomics: exact and the same
+ * from run to run.  -- csrc/polygon.hip
+ *   poly_rasterize : xy [nvert, 2] float64 (x, y) pixel coordinates; vert_offsets [npoly + 1] int32: polygon p owns vertices
+ *                    vert_offsets[p] .. vert_offsets[p + 1] - 1 (closed by the call); poly_offsets [nobj + 1] int32: object o owns
+ *                    polygons poly_offsets[o] .. poly_offsets[o + 1] - 1 -> masks [nobj, H, W] uint8 0 / 1 row-major, exactly the
+ *                    nobj * H * W bytes at ANY byte address, and area [nobj] int64 = the masks' foreground counts, both WRITTEN.
+ *                    An object without polygons gets an all-zero mask and area 0.  Per polygon: X = (int)(5 x + .5) (same for y), every
+ *                    edge walked in max(|dX|, |dY|) + 1 points with v = (int)(ys + s * t + .5); where the walk changes column, the
+ *                    column-major index (int)xd * H + ceil(clamp(yd, 0, H)) is recorded if xd = (u' + .5) / 5 - .5 is a pixel
+ *                    column; pixel p is set iff the number of recorded indices <= p is odd (= rleFrPoly's sort, difference and
+ *                    merge of empty runs; a recorded H * W has no effect).  Offsets and coordinates are data: a range is clamped to
+ *                    its array, a coordinate to +-65536 (a NaN reads as -65536), nothing is used as an index unchecked.
+ *                    workspace: ape_hip_poly_workspace_words(nobj, npoly, H, W) 64-bit words (negative: too large; H * W < 2^31),
+ *                    zeroed where needed by a memset node of the stream: a captured graph replays to the same result.
+ * Argument errors are reported before any HIP call; no allocation, no host synchronisation; nobj == 0 is a no-op.
+ * ------------------------------------------------------------------------------------------- */
+int ape_hip_poly_workspace_words(int nobj, int npoly, int H, int W);
+int ape_hip_poly_rasterize(const double* xy, int nvert, const int32_t* vert_offsets, int npoly, const int32_t* poly_offsets, int nobj,
+                           int H, int W, uint64_t* workspace, uint8_t* masks, int64_t* area, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
