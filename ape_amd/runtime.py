@@ -36,7 +36,6 @@ import os
 import queue
 import threading
 import weakref
-from types import SimpleNamespace
 
 import torch
 
@@ -62,14 +61,23 @@ def retired_graphs():
 
 class _DmaTransfer:
     """Helper thread that moves finished result slots to pinned host memory on a DMA ENGINE (csrc/hostcopy.cpp ape_hip_sdma_d2h).
-
     hipMemcpyAsync (what `tensor.copy_(..., non_blocking=True)` issues) runs a device -> pinned-host copy as a shader blit on this stack:
     a PCIe-bound kernel of ~1.9 ms per 105 MB image that keeps a few CUs occupied, so every GEMM launch with one workgroup per CU
     pays a second round while it runs (profiles/r06_d2h_blit_vs_sdma_probe.txt: +16-18 % on a GEMM loop with copies in flight, +0.2-1.1 %
     with the same bytes on the DMA engine).  The HSA copy is not stream-ordered, so this thread waits for the slot's `computed` event on
-    the host, issues the blocking copies (ctypes releases the GIL), and sets `done`; `GraphedForward.result()` waits for it."""
+    the host, issues the blocking copies (ctypes releases the GIL), and sets `done`; `_Slot.wait()` waits for it.
+    Where the pieces go is decided in the constructor -- when the first transfer is set up, on the submitting thread -- not inside each transfer:
+    it is an environment write (putenv), the main thread's launchers read the environment (getenv) on almost every launch, and the two must
+    not run concurrently.  The helper thread touches no environment at all; the library reads the variable, an explicit setting wins."""
 
     def __init__(self, device):
+        # pieces placed on the copy engines the runtime reports free for device -> host (the form measured inside the pipeline:
+        # profiles/r06_config5_transfer.txt); APE_SDMA_ENGINES=0 leaves the placement of the concurrent copies to the runtime
+        # ... in a single-process run.  With several ranks on one node (torch.distributed) the copies stay unplaced unless the environment says
+        # otherwise: explicit engine picks were only ever measured on 1-GPU boxes, and at 1024^2 (105 MB per image) one engine is enough
+        multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        os.environ.setdefault("APE_SDMA_ENGINES", "0" if multi else "1")
+        self.one_by_one = os.environ.get("APE_SDMA_MULTI") == "0"     # A/B: one blocking copy after the other (the first round-6 form)
         self.device = device
         self.q = queue.SimpleQueue()
         self.thread = threading.Thread(target=self._run, name="ape-dma-transfer", daemon=True)
@@ -89,22 +97,13 @@ class _DmaTransfer:
                 # every image's copy in flight at once, each in pieces over the free copy engines (one blocking copy after the other keeps
                 # one engine busy: the 2 x 1.18 GB per step of the 1536^2 / top-500 configuration then take longer than the step's kernels)
                 m = len(copies)
-                if os.environ.get("APE_SDMA_MULTI") == "0":   # A/B: one blocking copy after the other (the first round-6 form)
+                if self.one_by_one:
                     for dst, src, n in copies:
                         if lib.ape_hip_sdma_d2h(dst, src, n) != 0:
                             raise RuntimeError("ape_amd.runtime: " + (lib.ape_hip_last_error() or b"ape_hip_sdma_d2h failed").decode())
                     continue
-                # pieces placed on the copy engines the runtime reports free for device -> host (the form measured inside the pipeline:
-                # profiles/r06_config5_transfer.txt); APE_SDMA_ENGINES=0 leaves the placement of the concurrent copies to the runtime
-                # ... in a single-process run.  With several ranks on one node (torch.distributed) the copies stay unplaced unless the
-                # environment says otherwise: explicit engine picks were only ever measured on 1-GPU boxes, and at 1024^2 (105 MB per
-                # image) one engine is enough
-                multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
-                os.environ.setdefault("APE_SDMA_ENGINES", "0" if multi else "1")
-                dsts = (ctypes.c_void_p * m)(*[c[0] for c in copies])
-                srcs = (ctypes.c_void_p * m)(*[c[1] for c in copies])
-                sizes = (ctypes.c_size_t * m)(*[c[2] for c in copies])
-                if lib.ape_hip_sdma_d2h_multi(m, dsts, srcs, sizes, 0) != 0:
+                dsts, srcs, sizes = zip(*copies)
+                if lib.ape_hip_sdma_d2h_multi(m, (ctypes.c_void_p * m)(*dsts), (ctypes.c_void_p * m)(*srcs), (ctypes.c_size_t * m)(*sizes), 0) != 0:
                     raise RuntimeError("ape_amd.runtime: " + (lib.ape_hip_last_error() or b"ape_hip_sdma_d2h_multi failed").decode())
             except BaseException as exc:                      # surfaced by result()
                 err.append(exc)
@@ -133,6 +132,109 @@ class _Ticket:
         self.runs, self.mask_runs = None, None        # mask_format="rle": (device run lengths [B,k,cap], run counts [B,k]); all ranks'
 
 
+def _frame_row(frame_hw, model_hw):
+    """(sx, sy, sx, sy, width, height, width, height): an output frame (height, width) over a model input (h, w), as `_device_part` reads it"""
+    (fh, fw), (h, w) = frame_hw, model_hw
+    return [fw / w, fh / h, fw / w, fh / h, fw, fh, fw, fh]
+
+
+def _step_part(pipeline, partial_graphs, has_images, completes):
+    """the part of a step `_run_entry` runs: a pipelined stream starts with the ViT branch alone and ends (flush) with the tails alone"""
+    if pipeline and partial_graphs:
+        return "tails" if not has_images else ("full" if completes else "vit")
+    return "full"
+
+
+def _lane_plan(B, k, maxpix, pq, with_masks, mask_format, rle_cap, semantic, panoptic):
+    """the lanes of a result slot, in the order the copy stream moves them: [(name, shape, dtype, zero-filled, has a host half)]"""
+    rle = with_masks and mask_format in ("rle", "both")
+    lanes = [(True, "rec", (B, k, 8), torch.float32, False, True),
+             (semantic, "sem", (B, maxpix), torch.int16, False, True),
+             (panoptic, "pan", (B, maxpix), torch.int32, False, True),
+             (panoptic, "paninfo", (B, pq + 1, 3), torch.int32, True, True),   # the panoptic queries' segment table; last row: the segment count
+             (rle, "runs", (B, k, rle_cap), torch.int32, False, True),
+             (rle, "nruns", (B, k), torch.int32, True, True),
+             (with_masks, "masks", (B, k * maxpix), torch.uint8, False, mask_format != "rle")]     # "rle": only the runs travel
+    return [lane[1:] for lane in lanes if lane[0]]
+
+
+class _Slot:
+    """one result slot: device staging + pinned host buffers as lanes (name, device tensor, pinned tensor or None), each also reachable as
+    d_<name> / h_<name>; the two events that order its transfer; that transfer's state.  busy: holds results nobody has waited for yet."""
+    d_sem = h_sem = d_pan = h_pan = d_paninfo = h_paninfo = d_runs = h_runs = d_nruns = h_nruns = d_masks = h_masks = None    # absent lanes
+
+    def __init__(self, B, k, maxpix, pq, device, with_masks, mask_format, rle_cap, semantic, panoptic):
+        self.lanes = []
+        for name, shape, dtype, zero, host in _lane_plan(B, k, maxpix, pq, with_masks, mask_format, rle_cap, semantic, panoptic):
+            new = torch.zeros if zero else torch.empty
+            d = new(shape, dtype=dtype, device=device)
+            h = new(shape, dtype=dtype, pin_memory=True) if host else None
+            setattr(self, "d_" + name, d)
+            setattr(self, "h_" + name, h)
+            self.lanes.append((name, d, h))
+        self.computed, self.copied = torch.cuda.Event(), torch.cuda.Event()
+        self.busy, self.has_masks = False, False      # has_masks: the step in the slot pasted masks (set by _collect)
+        self.masks_done = self.masks_err = None       # the DMA-engine transfer of the masks: threading.Event, [exception]
+
+    def copy_out(self, copy_stream, frames, k, blit_masks):
+        """the lanes to pinned memory on the copy stream, between `computed` and `copied`; the masks only as a blit (else: a DMA engine)"""
+        with torch.cuda.stream(copy_stream):
+            copy_stream.wait_event(self.computed)
+            for name, d, h in self.lanes:
+                if name in ("runs", "nruns", "masks") and not self.has_masks:
+                    continue
+                if name != "masks":
+                    h.copy_(d, non_blocking=True)
+                elif blit_masks and h is not None:
+                    for b, (fh, fw) in enumerate(frames):
+                        h[b, : k * fh * fw].copy_(d[b, : k * fh * fw], non_blocking=True)
+            self.copied.record(copy_stream)
+
+    def wait(self):
+        """block until the slot's transfers have arrived; afterwards the slot is free again -- also when the DMA transfer's error is raised"""
+        try:
+            self.copied.synchronize()
+            if self.masks_done is not None:           # the DMA-engine transfer of the masks (helper thread)
+                self.masks_done.wait()
+                if self.masks_err:
+                    raise self.masks_err[0]
+        finally:
+            self.busy = False
+
+
+class _Entry:
+    """one captured step: its static input buffers, its graphs with their outputs, its ring of result slots.  (No closure over the entry is stored
+    on it: a reference cycle would leave the captured graphs to the garbage collector, i.e. destroy them; `pending` is weak for the same reason.)"""
+
+    def __init__(self, text=None, size=None, prompt="name", graph=None, graph_vit=None, graph_tails=None, pool_bytes=0):
+        self.text, self.prompt = text, prompt         # the text keeps the bank alive: the graph key holds its address
+        self.size = size                              # (height, width) of the output frame; any_size: of the S x S pad
+        self.images, self.frame = [], None            # static inputs: float [3, h, w] per image, frame rows [B, 8]
+        self.sgeo, self.mean_canvas = None, None      # any_size: StaticGeometry per image, the S x S canvas of per-channel means
+        self.feat, self.pending = None, None          # pipelined: ViT features of the waiting step, weakref of its ticket
+        self.graph, self.graph_vit, self.graph_tails = graph, graph_vit, graph_tails      # None: eager / no partial graphs
+        self.outs = self.outs_tails = None            # output tensors of the full / tails-only capture
+        self.pool_bytes = pool_bytes                  # the captures' private pools (what eviction parks)
+        self.k, self.maxpix = 0, 0                    # detections per image, largest output frame (pixels) a slot holds
+        self.slots, self.next_slot = [], 0            # the ring of result slots
+
+    def graphs(self):
+        return [g for g in (self.graph, self.graph_vit, self.graph_tails) if g is not None]
+
+    def replay(self, part):
+        """replay the captured `part` of the step -> its output tensors (without partial graphs: the full step)"""
+        g = {"full": self.graph, "vit": self.graph_vit, "tails": self.graph_tails}[part] or self.graph
+        g.replay()
+        return self.outs_tails if g is self.graph_tails else self.outs
+
+    def claim_slot(self):
+        """the next slot of the ring; it is busy from the moment its step is enqueued until its `wait()`"""
+        s = self.slots[self.next_slot]
+        if s.busy:
+            raise RuntimeError("GraphedForward.submit: every result slot is outstanding -- call result() on an earlier ticket first")
+        self.next_slot = (self.next_slot + 1) % len(self.slots)
+        return s
+
 
 class GraphedForward:
     SLOTS = 2
@@ -140,6 +242,16 @@ class GraphedForward:
     def __init__(self, model_vision, use_graph=True, max_graphs=16, with_masks=True, images_per_step=1, batch_vit=True,
                  pipeline=False, any_size=False, max_out_pixels=None, mask_format="bitmask", rle_cap=4096, semantic=None, panoptic=None,
                  input_resize=(1024, 1024), input_format="RGB"):
+        # pipelined steps: start the ViT branch behind the tails' encoders (see _run_entry); APE_PIPE_LATE_VIT=0|1 overrides
+        self.late_vit = os.environ.get("APE_PIPE_LATE_VIT", "0") == "1"
+        # pipelined steps: the first step of a stream / the flush behind its last step run as ViT-only / tails-only graphs (see
+        # _build); APE_PIPE_PARTIAL=0 replays the full step there, as rounds 2-5 did
+        self.partial_graphs = os.environ.get("APE_PIPE_PARTIAL", "1") != "0"
+        # mask transfer: "sdma" = the library's DMA-engine copy on a helper thread (default), "blit" = hipMemcpyAsync on the copy stream
+        # (a shader blit on this stack; rounds 1-5) -- APE_D2H=blit|sdma
+        self.d2h = os.environ.get("APE_D2H", "sdma")
+        if self.d2h not in ("sdma", "blit"):
+            raise ValueError("APE_D2H is 'sdma' or 'blit'")
         self.mv = model_vision
         # uint8 inputs (the predictor's contract, ape/engine/defaults.py:213-222: the ORIGINAL BGR image): submit() takes uint8
         # [H, W, 3] tensors -- pinned host memory or device -- and runs upload + ResizeShortestEdge(short_edge_length, max_size)
@@ -178,40 +290,31 @@ class GraphedForward:
         # logits (fixed shapes); the merge itself -- crop to the image's own (h, w), resize to its output frame, the walk over
         # the queries: three launches, no host round trip -- runs behind the replay with the ticket's sizes, like the mask paste.
         self.panoptic = panoptic
-        # pipelined steps: start the ViT branch behind the tails' encoders (see _run_entry); APE_PIPE_LATE_VIT=0|1 overrides
-        self.late_vit = os.environ.get("APE_PIPE_LATE_VIT", "0") == "1"
-        # pipelined steps: the first step of a stream / the flush behind its last step run as ViT-only / tails-only graphs (see
-        # _build); APE_PIPE_PARTIAL=0 replays the full step there, as rounds 2-5 did
-        self.partial_graphs = os.environ.get("APE_PIPE_PARTIAL", "1") != "0"
         self._graphs = {}
         self._copy_stream = None
-        # mask transfer: "sdma" = the library's DMA-engine copy on a helper thread (default), "blit" = hipMemcpyAsync on the copy stream
-        # (a shader blit on this stack; rounds 1-5) -- APE_D2H=blit|sdma
-        self.d2h = os.environ.get("APE_D2H", "sdma")
-        if self.d2h not in ("sdma", "blit"):
-            raise ValueError("APE_D2H is 'sdma' or 'blit'")
         self._dma = None
 
     def _retire(self, entry, strict=True):
-        if getattr(entry, "graph", None) is None:
+        """park the entry's graphs: the full graph with the bytes of the captures' pools (they span all three captures of a pipelined
+        entry) and its partial graphs with none -- or, when the limit refuses, nothing at all"""
+        entry = entry if isinstance(entry, _Entry) else _Entry(**vars(entry))      # anything that carries an entry's fields
+        graphs = entry.graphs()
+        if not graphs:                                    # eager entries hold no graph
             return
-        for name in ("graph_vit", "graph_tails"):         # the partial graphs of a pipelined entry share its fate (and its byte count)
-            if getattr(entry, name, None) is not None:
-                _RETIRED.append((getattr(entry, name), 0))
-        nbytes = int(getattr(entry, "pool_bytes", 0))
+        nbytes = int(entry.pool_bytes)
         n, held = retired_graphs()
         if strict and held + nbytes > RETIRE_LIMIT_BYTES:
             raise RuntimeError(
-                f"GraphedForward: evicting this graph would park {(held + nbytes) / (1 << 30):.1f} GB of HBM in {n + 1} retired hipGraphs "
+                f"GraphedForward: evicting this graph would park {(held + nbytes) / (1 << 30):.1f} GB of HBM in {n + len(graphs)} retired hipGraphs "
                 f"(limit {RETIRE_LIMIT_BYTES / (1 << 30):.0f} GB, APE_GRAPH_RETIRE_LIMIT_GB).  Captured graphs are never destroyed on this "
                 "stack, so a stream that keeps changing (image size, vocabulary, frame) grows without bound: use any_size=True (one "
                 f"size-agnostic graph), raise max_graphs (now {self.max_graphs}) above the number of distinct keys, or raise the limit.")
-        _RETIRED.append((entry.graph, nbytes))
+        _RETIRED.extend((g, nbytes if g is entry.graph else 0) for g in graphs)
 
     def memory_report(self):
         """{"live_graphs", "live_bytes", "retired_graphs", "retired_bytes", "retire_limit_bytes"}: HBM held by captured steps"""
         n, held = retired_graphs()
-        return {"live_graphs": len(self._graphs), "live_bytes": sum(int(getattr(e, "pool_bytes", 0)) for e in self._graphs.values()),
+        return {"live_graphs": len(self._graphs), "live_bytes": sum(int(e.pool_bytes) for e in self._graphs.values()),
                 "retired_graphs": n, "retired_bytes": held, "retire_limit_bytes": RETIRE_LIMIT_BYTES}
 
     def __del__(self):
@@ -228,7 +331,6 @@ class GraphedForward:
         """everything up to (excluding) the mask paste: (record [k,8], 128x128 masks or None, boxes in the output frame).
         frame: device vector [8] = (sx, sy, sx, sy, width, height, width, height) of the output frame (rewritten per image
         with any_size, constant otherwise)."""
-        import math
         from . import ops
         mv = self.mv
         out = mv.forward_single(image, text, with_masks=self.with_masks, prompt=prompt, vit_feat=vit_feat, geo=geo,
@@ -331,7 +433,7 @@ class GraphedForward:
             jobs = [ops.fork(lambda b=b: self._tail(e, b, feats[b]), force=True) for b in range(1, B)]
             return [self._tail(e, 0, feats[0])] + [j.join() for j in jobs]
 
-    # ------------------------------------------------------------------ inputs: float CHW model images or uint8 HWC originals
+    # ------------------------------------------------------------------ inputs: float CHW model images or uint8 HWC originals; any_size: + geometry
     @staticmethod
     def _is_raw(im):
         return im.dtype == torch.uint8 and im.dim() == 3 and im.shape[-1] == 3
@@ -353,37 +455,27 @@ class GraphedForward:
         raw = im if im.is_cuda else im.to(dst.device, non_blocking=True)
         ops.resize_bilinear_u8(raw.contiguous(), dst.shape[-2], dst.shape[-1], out=dst, float_chw=True, flip=self.input_flip)
 
-    # ------------------------------------------------------------------ per-image inputs of the size-agnostic graph
-    def _level_shapes(self):
-        S = self.mv.backbone.padding_constraints.get("square_size", 0)
-        strides = [self.mv.backbone._out_feature_strides[f] for f in self.mv.neck.in_features]
-        return S, [(S // st, S // st) for st in strides]
-
-    def _geometry_into(self, sgeo, S, h, w):
-        """the constants of an (h, w) image, generated on the device into the graph's fixed buffers (one launch)"""
-        mv = self.mv
-        if not mv.position_embedding.normalize:
-            raise NotImplementedError("ape_amd: the geometry kernel implements the normalised sine embedding of the APE configs")
-        sgeo.generate(S, (h, w), mv.pos_cfg(), mv.transformer.packed(mv.compute_dtype)["level_embeds"])
-
-    def _load_inputs(self, e, images, frames):
-        """any_size: write image b into its canvas, the constants of its (h, w) into its StaticGeometry, and its output frame
-        into the frame vector -- all stream-ordered in front of the replay"""
-        mv = self.mv
-        S, shapes = self._level_shapes()
-        dt = mv.compute_dtype
-        vals = []
-        for b, im in enumerate(images):
-            h, w = self._model_hw(im)
+    def _write_canvas(self, e, b, im, h, w):
+        """image b, h x w as a model input, into its static buffer; any_size: into its S x S canvas of means, which it has to fit"""
+        if self.any_size:
+            S = e.size[0]
             if h > S or w > S:
                 raise ValueError(f"GraphedForward(any_size): image {h}x{w} does not fit the {S}x{S} pad")
             e.images[b].copy_(e.mean_canvas, non_blocking=True)
-            self._write_input(e.images[b][:, :h, :w], im)
-            self._geometry_into(e.sgeo[b], S, h, w)
-            height, width = frames[b]
-            sx, sy = width / w, height / h
-            vals.append([sx, sy, sx, sy, width, height, width, height])
-        e.frame.copy_(torch.tensor(vals, dtype=torch.float32))              # pageable source: staged before the call returns
+        self._write_input(e.images[b][:, :h, :w], im)
+
+    def _stage(self, e, images, mhw, frames, canvas=True, geometry=False):
+        """the stream-ordered writes of a step's inputs, image by image (mhw: their model sizes): with `canvas` the image into its buffer; with
+        `geometry` (any_size) the constants of its (h, w) into its StaticGeometry and -- behind the last image -- the frame vector"""
+        mv, rows = self.mv, []
+        for b, (im, (h, w)) in enumerate(zip(images, mhw)):
+            if canvas:
+                self._write_canvas(e, b, im, h, w)
+            if geometry:        # generated on the device into the graph's fixed buffers (one launch)
+                e.sgeo[b].generate(e.size[0], (h, w), mv.pos_cfg(), mv.transformer.packed(mv.compute_dtype)["level_embeds"])
+                rows.append(_frame_row(frames[b], (h, w)))
+        if geometry:
+            e.frame.copy_(torch.tensor(rows, dtype=torch.float32))          # pageable source: staged before the call returns
 
     # ------------------------------------------------------------------ capture
     def _build(self, images, text, height, width, prompt):
@@ -391,40 +483,33 @@ class GraphedForward:
         mv = self.mv
         dev = next(mv.parameters()).device
         B = len(images)
-        e = SimpleNamespace()
-        e.text = text                 # keeps the bank alive: the graph key holds its address
-        e.size, e.prompt = (height, width), prompt
+        mhw = [self._model_hw(im) for im in images]
         # warm-up and capture run fusion_tokens, which (phrase / expression prompts, persistent bank) shifts the phrase bank
         # in place: snapshot it and restore it afterwards so that building a graph does not count as three extra images
-        bank = mv.features_phrase_bank.clone() if getattr(mv, "text_feature_bank", False) else None
+        bank = mv.features_phrase_bank.clone() if mv.text_feature_bank else None
         if self.any_size:
-            S, shapes = self._level_shapes()
-            dt = mv.compute_dtype
+            if not mv.position_embedding.normalize:
+                raise NotImplementedError("ape_amd: the geometry kernel implements the normalised sine embedding of the APE configs")
+            S = mv.backbone.padding_constraints.get("square_size", 0)
+            shapes = [(S // mv.backbone._out_feature_strides[f],) * 2 for f in mv.neck.in_features]
+            e = _Entry(text, (S, S), prompt)
             e.mean_canvas = torch.tensor(mv._mean, dtype=torch.float32, device=dev).view(3, 1, 1).expand(3, S, S).contiguous()
             e.images = [e.mean_canvas.clone() for _ in range(B)]
             g0 = mv.geometry((S, S), shapes)
-            lp = mv.transformer.lvl_pos(g0, dt)
+            lp = mv.transformer.lvl_pos(g0, mv.compute_dtype)
             key = next(iter(g0._lvl_pos))
             e.sgeo = [StaticGeometry(g0, key, lp) for _ in range(B)]
             e.frame = torch.zeros((B, 8), dtype=torch.float32, device=dev)
-            self._load_inputs(e, images, [self._model_hw(im) for im in images])
-            e.size = (S, S)
+            self._stage(e, images, mhw, mhw, geometry=True)   # the capture's own output frame: each image's model size
         else:
-            e.images = []
-            vals = []
-            for im in images:
-                mh, mw = self._model_hw(im)
-                e.images.append(torch.empty((3, mh, mw), dtype=torch.float32, device=dev))
-                self._write_input(e.images[-1], im)
-                sx, sy = width / mw, height / mh
-                vals.append([sx, sy, sx, sy, width, height, width, height])
-            e.frame = torch.tensor(vals, dtype=torch.float32).to(dev)
+            e = _Entry(text, (height, width), prompt)
+            e.images = [torch.empty((3, mh, mw), dtype=torch.float32, device=dev) for mh, mw in mhw]
+            self._stage(e, images, mhw, None)
+            e.frame = torch.tensor([_frame_row((height, width), m) for m in mhw], dtype=torch.float32).to(dev)
         if self.pipeline:
             net = mv.backbone.net
             n_tok = (net.img_size // net.patch_size) ** 2
             e.feat = torch.zeros((B * n_tok, net.embed_dim), dtype=mv.compute_dtype, device=dev)
-            e.pending = None          # weakref of the ticket whose ViT features sit in e.feat, tails not run yet
-        # (no closure over `e` is stored on it: a reference cycle would leave the captured graph to the garbage collector)
         for _ in range(2):            # warm every cache (weight packing, geometry, text side) outside the capture
             self._run_entry(e)
         torch.cuda.synchronize()
@@ -437,7 +522,6 @@ class GraphedForward:
             # flush behind the last step has no new ones (tails only).  Replaying the FULL step there ran one ViT pass and B tails
             # nobody consumed per stream: K steps cost K + 1 full replays (5 % of a 20-step run).  Same launches, same static
             # buffers, the part's own output tensors.
-            e.graph_vit = e.graph_tails = None
             if self.pipeline and self.partial_graphs:
                 e.graph_vit = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(e.graph_vit):
@@ -446,40 +530,15 @@ class GraphedForward:
                 with torch.cuda.graph(e.graph_tails):
                     e.outs_tails = self._run_entry(e, "tails")
             e.pool_bytes = max(0, torch.cuda.memory_reserved() - reserved)      # the captures' private pools (what eviction parks)
-        else:
-            e.graph = e.graph_vit = e.graph_tails = None
         if bank is not None:
             mv.features_phrase_bank.copy_(bank)
-        k = 1 if prompt == "expression" else mv.test_topk_per_image       # (:183-194) one box per referring expression
-        has_masks = self.with_masks and mv.test_mask_on
-        e.k = k
+        k = e.k = 1 if prompt == "expression" else mv.test_topk_per_image       # (:183-194) one box per referring expression
         e.maxpix = (self.max_out_pixels or e.size[0] * e.size[1]) if self.any_size else height * width
-        e.slots = []
         # rows of the panoptic segment table = the step's panoptic queries (the class-wise NMS keeps test_topk_per_image of them;
         # all queries without panoptic_post_nms)
         pq = (k if mv.panoptic_post_nms else mv.num_queries) if self.panoptic is not None else 0
-        for _ in range(self.SLOTS):
-            s = SimpleNamespace()
-            s.d_rec = torch.empty((B, k, 8), dtype=torch.float32, device=dev)
-            s.h_rec = torch.empty((B, k, 8), dtype=torch.float32, pin_memory=True)
-            s.d_masks = torch.empty((B, k * e.maxpix), dtype=torch.uint8, device=dev) if has_masks else None
-            rle = has_masks and self.mask_format in ("rle", "both")
-            s.h_masks = torch.empty((B, k * e.maxpix), dtype=torch.uint8, pin_memory=True) if has_masks and self.mask_format != "rle" else None
-            s.d_runs = torch.empty((B, k, self.rle_cap), dtype=torch.int32, device=dev) if rle else None
-            s.d_nruns = torch.zeros((B, k), dtype=torch.int32, device=dev) if rle else None
-            s.h_runs = torch.empty((B, k, self.rle_cap), dtype=torch.int32, pin_memory=True) if rle else None
-            s.h_nruns = torch.zeros((B, k), dtype=torch.int32, pin_memory=True) if rle else None
-            s.d_sem = torch.empty((B, e.maxpix), dtype=torch.int16, device=dev) if self.semantic is not None else None
-            s.h_sem = torch.empty((B, e.maxpix), dtype=torch.int16, pin_memory=True) if self.semantic is not None else None
-            # panoptic: the map + the segment table of the step's panoptic queries (one extra row carries the segment count)
-            s.d_pan = torch.empty((B, e.maxpix), dtype=torch.int32, device=dev) if self.panoptic is not None else None
-            s.h_pan = torch.empty((B, e.maxpix), dtype=torch.int32, pin_memory=True) if self.panoptic is not None else None
-            s.d_paninfo = torch.zeros((B, pq + 1, 3), dtype=torch.int32, device=dev) if self.panoptic is not None else None
-            s.h_paninfo = torch.zeros((B, pq + 1, 3), dtype=torch.int32, pin_memory=True) if self.panoptic is not None else None
-            s.computed, s.copied = torch.cuda.Event(), torch.cuda.Event()
-            s.busy = False
-            e.slots.append(s)
-        e.next_slot = 0
+        e.slots = [_Slot(B, k, e.maxpix, pq, dev, self.with_masks and mv.test_mask_on, self.mask_format, self.rle_cap,
+                         self.semantic is not None, self.panoptic is not None) for _ in range(self.SLOTS)]
         return e
 
     # ------------------------------------------------------------------ pipelined interface
@@ -525,148 +584,90 @@ class GraphedForward:
             raise ValueError(f"GraphedForward.submit: output frame larger than max_out_pixels={e.maxpix}")
         t = _Ticket(e, single, frames, mhw)
         if not self.pipeline:
-            self._replay(e, images, frames, completes=t)
+            self._replay(e, images, mhw, frames, completes=t)
             return t
         # pipelined: this replay runs the tails of the PREVIOUS ticket and the ViT of these images
-        self._replay(e, images, frames, completes=e.pending() if e.pending is not None else None)
+        self._replay(e, images, mhw, frames, completes=e.pending() if e.pending is not None else None)
         e.pending = weakref.ref(t)        # weak: ticket -> entry -> ticket would be a cycle; a dropped ticket's detections
         return t                          # are simply not delivered
 
-    def _replay(self, e, images, frames, completes):
-        """enqueue one step (graph replay or eager run) and, for the ticket whose detections it produces, the mask paste into a
-        result slot and the slot's transfer to pinned memory on the copy stream"""
-        from . import ops
-        s = None
-        if completes is not None:
-            s = e.slots[e.next_slot]
-            if s.busy:
-                raise RuntimeError("GraphedForward.submit: every result slot is outstanding -- call result() on an earlier ticket first")
-            e.next_slot = (e.next_slot + 1) % self.SLOTS
-        cur = torch.cuda.current_stream()
-        if images is not None and not (self.pipeline and self.any_size):
-            if self.any_size:
-                self._load_inputs(e, images, frames)
-            else:
-                for buf, im in zip(e.images, images):
-                    self._write_input(buf, im)
-        elif images is not None:
-            # pipelined + any_size: the canvases feed the ViT of THIS replay (new images), the static geometry / frame feed its
-            # tails (previous images).  Canvases are loaded now; geometry and frame of the new images after the replay.
-            S = e.size[0]
-            for b, im in enumerate(images):
-                h, w = self._model_hw(im)
-                if h > S or w > S:
-                    raise ValueError(f"GraphedForward(any_size): image {h}x{w} does not fit the {S}x{S} pad")
-                e.images[b].copy_(e.mean_canvas, non_blocking=True)
-                self._write_input(e.images[b][:, :h, :w], im)
-        part = "full"
-        if self.pipeline and self.partial_graphs:
-            part = "tails" if images is None else ("vit" if completes is None else "full")
-        if e.graph is not None:
-            g = {"full": e.graph, "vit": e.graph_vit, "tails": e.graph_tails}[part]
-            if g is None:
-                g, part = e.graph, "full"
-            g.replay()
-            outs = e.outs_tails if part == "tails" else e.outs
-        else:
-            outs = self._run_entry(e, part)
-        if completes is not None:
-            cur.wait_event(s.copied)                      # the slot's previous transfer has left the staging buffers
-            has_masks = s.d_masks is not None and outs[0][1] is not None
-            k = e.k
-            for b, (rec, masks128, boxes, labels, pan) in enumerate(outs):
-                s.d_rec[b].copy_(rec, non_blocking=True)
-                if labels is not None:
-                    if self.any_size:           # class scores over the pad -> this image's region -> its output frame
-                        mh, mw = completes.model_hw[b]
-                        labels = self._sem_labels(labels[:, :mh, :mw], *completes.frames[b])
-                    s.d_sem[b, : labels.numel()].copy_(labels.reshape(-1), non_blocking=True)
-                if pan is not None:
-                    if self.any_size:           # mask logits over the pad -> this image's region -> merged in its output frame
-                        mh, mw = completes.model_hw[b]
-                        pan = self.mv.panoptic_device(dict(pan, pan_masks=pan["pan_masks"][:, :mh, :mw]), *completes.frames[b], self.panoptic)
-                    s.d_pan[b, : pan[0].numel()].copy_(pan[0].reshape(-1), non_blocking=True)
-                    s.d_paninfo[b, : pan[1].shape[0]].copy_(pan[1], non_blocking=True)
-                    s.d_paninfo[b, -1, 0:1].copy_(pan[2], non_blocking=True)        # last row, column 0: the segment count
-                if has_masks:
-                    fh, fw = completes.frames[b]
-                    pasted = ops.paste_bits(masks128, boxes, fh, fw, out=s.d_masks[b, : k * fh * fw].view(k, fh, fw))   # detector_postprocess (:869-871)
-                    if s.d_runs is not None:
-                        ops.rle_encode(pasted, cap=self.rle_cap, counts=s.d_runs[b], nruns=s.d_nruns[b])
-            s.computed.record(cur)
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(s.computed)
-                s.h_rec.copy_(s.d_rec, non_blocking=True)
-                if s.d_sem is not None:
-                    s.h_sem.copy_(s.d_sem, non_blocking=True)
-                if s.d_pan is not None:
-                    s.h_pan.copy_(s.d_pan, non_blocking=True)
-                    s.h_paninfo.copy_(s.d_paninfo, non_blocking=True)
-                if has_masks and s.d_runs is not None:
-                    s.h_runs.copy_(s.d_runs, non_blocking=True)
-                    s.h_nruns.copy_(s.d_nruns, non_blocking=True)
-                if has_masks and s.h_masks is not None and self.d2h == "blit":
-                    for b in range(len(outs)):
-                        fh, fw = completes.frames[b]
-                        s.h_masks[b, : k * fh * fw].copy_(s.d_masks[b, : k * fh * fw], non_blocking=True)
-                s.copied.record(self._copy_stream)
+    def _replay(self, e, images, mhw, frames, completes):
+        """enqueue one step and, for the ticket whose detections it produces, the paste into a result slot and the slot's transfers.  In this order --
+        current stream: [per new image: canvas (any_size, not pipelined: + geometry); then the frame vector] -> the step (replay or eager) ->
+          wait(slot.copied) -> per image: record, labels, panoptic merge, paste (+ rle) -> record(slot.computed) -> [late geometry, frame];
+        copy stream: wait(slot.computed) -> rec, sem, pan, paninfo, runs, nruns, (blit: masks per image) -> record(slot.copied);
+        DMA thread (sdma): host wait on slot.computed -> the masks."""
+        s = e.claim_slot() if completes is not None else None
+        # pipelined + any_size: the canvases feed the ViT of THIS replay (new images), the static geometry / frame feed its
+        # tails (previous images).  Canvases are loaded now; geometry and frame of the new images after the replay.
+        late_geometry = self.pipeline and self.any_size
+        if images is not None:
+            self._stage(e, images, mhw, frames, geometry=self.any_size and not late_geometry)
+        part = _step_part(self.pipeline, self.partial_graphs, images is not None, completes is not None)
+        outs = e.replay(part) if e.graph is not None else self._run_entry(e, part)
+        if s is not None:
+            self._collect(outs, s, completes)
+            s.copy_out(self._copy_stream, completes.frames, e.k, blit_masks=self.d2h == "blit")
             s.masks_done = s.masks_err = None
-            if has_masks and s.h_masks is not None and self.d2h == "sdma":
+            if s.has_masks and s.h_masks is not None and self.d2h == "sdma":
                 # the [k, H, W] masks (105 MB per 1024^2 image) leave on a DMA engine: the helper thread waits for `computed` on the host.
                 # The slot is not reused before result() has waited for this transfer (s.busy), so no stream-side ordering is needed.
                 if self._dma is None:
                     self._dma = _DmaTransfer(s.d_masks.device)
-                copies = [(s.h_masks[b].data_ptr(), s.d_masks[b].data_ptr(), k * completes.frames[b][0] * completes.frames[b][1])
-                          for b in range(len(outs))]
+                copies = [(s.h_masks[b].data_ptr(), s.d_masks[b].data_ptr(), e.k * fh * fw) for b, (fh, fw) in enumerate(completes.frames)]
                 s.masks_done, s.masks_err = self._dma.submit(s.computed, copies)
             s.busy = True
-            s.has_masks = has_masks
             completes.slot, completes.ready = s, True
             completes.rec6 = s.d_rec[:, :, :6] if self.B > 1 else s.d_rec[0, :, :6]
-            if has_masks and s.d_runs is not None:
+            if s.has_masks and s.d_runs is not None:
                 completes.runs = (s.d_runs, s.d_nruns)
-        if images is not None and self.pipeline and self.any_size:
-            # now the static geometry / frame may take the NEW images' constants (stream-ordered behind the replay)
-            mv = self.mv
-            S, shapes = self._level_shapes()
-            vals = []
-            for b, im in enumerate(images):
-                h, w = self._model_hw(im)
-                self._geometry_into(e.sgeo[b], S, h, w)
-                fh, fw = frames[b]
-                sx, sy = fw / w, fh / h
-                vals.append([sx, sy, sx, sy, fw, fh, fw, fh])
-            e.frame.copy_(torch.tensor(vals, dtype=torch.float32))          # pageable source: staged before the call returns
+        if images is not None and late_geometry:          # stream-ordered behind the replay: the NEW images' constants may go in
+            self._stage(e, images, mhw, frames, canvas=False, geometry=True)
+
+    def _collect(self, outs, s, ticket):
+        """the per-image work behind the step, on the current stream and with the ticket's sizes, into the staging buffers of slot `s`; then `computed`"""
+        from . import ops
+        cur, k = torch.cuda.current_stream(), ticket.entry.k
+        cur.wait_event(s.copied)                          # the slot's previous transfer has left the staging buffers
+        s.has_masks = s.d_masks is not None and outs[0][1] is not None
+        for b, (rec, masks128, boxes, labels, pan) in enumerate(outs):
+            (mh, mw), (fh, fw) = ticket.model_hw[b], ticket.frames[b]
+            s.d_rec[b].copy_(rec, non_blocking=True)
+            if labels is not None:
+                if self.any_size:               # class scores over the pad -> this image's region -> its output frame
+                    labels = self._sem_labels(labels[:, :mh, :mw], fh, fw)
+                s.d_sem[b, : labels.numel()].copy_(labels.reshape(-1), non_blocking=True)
+            if pan is not None:
+                if self.any_size:               # mask logits over the pad -> this image's region -> merged in its output frame
+                    pan = self.mv.panoptic_device(dict(pan, pan_masks=pan["pan_masks"][:, :mh, :mw]), fh, fw, self.panoptic)
+                s.d_pan[b, : pan[0].numel()].copy_(pan[0].reshape(-1), non_blocking=True)
+                s.d_paninfo[b, : pan[1].shape[0]].copy_(pan[1], non_blocking=True)
+                s.d_paninfo[b, -1, 0:1].copy_(pan[2], non_blocking=True)            # last row, column 0: the segment count
+            if s.has_masks:
+                pasted = ops.paste_bits(masks128, boxes, fh, fw, out=s.d_masks[b, : k * fh * fw].view(k, fh, fw))   # detector_postprocess (:869-871)
+                if s.d_runs is not None:
+                    ops.rle_encode(pasted, cap=self.rle_cap, counts=s.d_runs[b], nruns=s.d_nruns[b])
+        s.computed.record(cur)
 
     def flush(self, entry=None):
         """pipelined mode: run the tails of the ticket whose ViT features are waiting (one replay of the tails-only graph)"""
         for e in ([entry] if entry is not None else list(self._graphs.values())):
             if self.pipeline and e.pending is not None:
                 t, e.pending = e.pending(), None
-                self._replay(e, None, None, completes=t)
+                self._replay(e, None, None, None, completes=t)
 
     def result(self, ticket):
         """wait for the ticket's transfer; returns (instances on the host, device record view [k,6]) -- lists / [B,k,6] when the
         step was submitted as a list.  pred_masks is a zero-copy view of the slot's pinned buffer: valid until SLOTS further
         completed steps.  Pipelined mode: a ticket completes with the NEXT submit; asking earlier flushes the pipeline."""
-        e = ticket.entry
         if not ticket.ready:
-            self.flush(e)
-        s = ticket.slot
-        s.copied.synchronize()
-        if s.masks_done is not None:                        # the DMA-engine transfer of the masks (helper thread)
-            s.masks_done.wait()
-            if s.masks_err:
-                raise s.masks_err[0]
-        s.busy = False
-        insts = []
-        k = e.k
-        for b in range(self.B):
+            self.flush(ticket.entry)
+        s, k, insts = ticket.slot, ticket.entry.k, []
+        s.wait()
+        for b, (fh, fw) in enumerate(ticket.frames):
             hr = s.h_rec[b]
             n = int((hr[:, 7] > 0.5).sum())                 # kept detections are a prefix (sorted on the device)
-            fh, fw = ticket.frames[b]
-            extra = {}
-            masks = None
+            masks, extra = None, {}
             if s.has_masks and s.h_runs is not None:
                 extra["pred_masks_rle"] = self._rles(s, b, n, fh, fw)
             if s.has_masks and s.h_masks is not None:
@@ -678,9 +679,7 @@ class GraphedForward:
         if s.h_pan is not None:       # (panoptic_seg view of the slot's pinned buffer, segments_info) per image
             ticket.panoptic = [(s.h_pan[b, : fh * fw].view(fh, fw), self.mv.segments_info(s.h_paninfo[b, :-1], s.h_paninfo[b, -1, 0:1]))
                                for b, (fh, fw) in enumerate(ticket.frames)]
-        if ticket.single:
-            return insts[0], ticket.rec6
-        return insts, ticket.rec6
+        return (insts[0] if ticket.single else insts), ticket.rec6
 
     def _rles(self, s, b, n, fh, fw):
         """COCO RLE dicts of the first n (kept) detections of image b of slot s; a mask with more runs than the slot's buffer
